@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """DFormer-Base + ham decoder, 480x640, bs=16 per GPU, bf16 training-step throughput (images/s).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   (N > 1: one rank per GPU over RCCL/xGMI. Launched by torch.distributed.run it uses the
   WORLD_SIZE/RANK/LOCAL_RANK it finds; started directly with --gpus N > 1 it re-launches itself
   under torch.distributed.run as a child process before touching the GPU.)
@@ -9,10 +9,15 @@
 One step = forward + fused CE loss + backward (bucketed RCCL all-reduce overlapped) + fused AdamW,
 on synthetic inputs resident in HBM (BASELINE.json config 3 / 4). Rank 0 prints one JSON line:
 whole-job images/s over the K timed steps (barrier + synchronize on both sides, max over ranks),
-per-step median / p10 / p90, the roofline of the dominant kernel and of the whole step, and the
-CPU-oracle baseline.
+ms_per_step (the same wall time / K) and the per-step median / p10 / p90.
 
-Measurement:
+A plain run does only that: set up, W warm-up steps, the K timed steps, the result line.
+--dump-outputs DIR then writes what the last timed step left (DIR/<name>.npy, see dump_outputs).
+--full adds everything else: the census step, the roofline of the dominant kernel and of the whole
+step (--table-out writes the per-kernel table) and the CPU-oracle baseline; --no-census and
+--no-cpu-baseline drop one of them again.
+
+Measurement under --full:
   * census step (untimed, after warm-up): the library's launch tracer times every kernel it
     launches with HIP events on the launching stream, and kernels.ACCOUNT charges every entry
     point's algorithmic FLOPs / HBM bytes to the kernel it launched -> per-kernel table
@@ -67,13 +72,22 @@ def parse():
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"],
                     help="compute dtype; fp16 = the reference's --amp (dynamic loss scaling decided on the device, graph replay)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU-oracle baseline out")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-census", action="store_true")
+    ap.add_argument("--no-census", action="store_true", help="with --full: leave the census step and the rooflines out")
     ap.add_argument("--eager", action="store_true",
                     help="issue every kernel from Python each step instead of replaying the captured HIP graph")
-    ap.add_argument("--table-out", default=None, help="write the per-kernel F/B/time table (JSON) here")
-    return ap.parse_args()
+    ap.add_argument("--table-out", default=None, help="write the per-kernel F/B/time table (JSON) here (needs --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the census step, the dominant-kernel / step rooflines and the CPU-oracle baseline")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.table_out and not args.full:
+        ap.error("--table-out is written from the census step: it needs --full")
+    return args
 
 
 def relaunch_distributed(args):
@@ -258,6 +272,39 @@ def cpu_baseline(model_sd, seconds):
                                   f"{n_tiny} timed iters"}}
 
 
+DUMP_SAMPLE = 4 << 20  # elements kept per dumped array: 16 MB as float32
+
+
+def dump_outputs(path, model, opt, loss):
+    """What a caller of the timed step holds after its last step, as float32 <path>/<name>.npy:
+      loss    the step's return value (the mean CE loss)
+      params  every trainable parameter after that step's AdamW update, flattened and concatenated
+              in model.parameters() order
+      grads   the gradients that update consumed (the optimizer's flat gradient buffers, loss-scaled
+              under fp16), in the same order; parameters in no optimizer group are left out
+    params / grads longer than DUMP_SAMPLE elements are cut to a fixed, seeded, sorted sample of
+    their positions: the same positions in every run of one configuration."""
+    import numpy as np
+    import torch
+    params = [p for p in model.parameters() if p.requires_grad]
+    grads = []
+    for p in params:
+        for g in opt.groups:
+            if p in g.slots:
+                off, k = g.slots[p]
+                grads.append(g.grad[off:off + k])
+    out = {"loss": loss.detach().reshape(1),
+           "params": torch.cat([p.detach().reshape(-1) for p in params]),
+           "grads": torch.cat(grads)}
+    os.makedirs(path, exist_ok=True)
+    for name, t in out.items():
+        if t.numel() > DUMP_SAMPLE:
+            gen = torch.Generator().manual_seed(8964)
+            idx = torch.randperm(t.numel(), generator=gen)[:DUMP_SAMPLE].sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -284,7 +331,9 @@ def main():
     for m in model.decode_head.modules():  # init_func.init_weight: kaiming on decoder convs
         if isinstance(m, torch.nn.Conv2d):
             torch.nn.init.kaiming_normal_(m.weight, mode="fan_in", nonlinearity="relu")
-    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if rank == 0 else None
+    want_census = args.full and not args.no_census
+    want_cpu = args.full and world == 1 and not args.no_cpu_baseline
+    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()} if rank == 0 and want_cpu else None
     cdt = torch.float16 if args.dtype == "fp16" else torch.bfloat16
     model = model.to(dev).set_compute_dtype(cdt)
     if world > 1:
@@ -301,7 +350,7 @@ def main():
     for _ in range(args.warmup):
         step()
     table, dom, probes = None, None, []
-    if not args.no_census:
+    if want_census:
         table = census(step)
         probes = probed_kernels(table)
         dom = probes[0]
@@ -334,6 +383,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = torch.tensor([time.perf_counter() - t0], device=dev, dtype=torch.float64)
+    if args.dump_outputs and rank == 0:  # before the probe steps below move the parameters on
+        dump_outputs(args.dump_outputs, model, opt, loss)
     dom_ms = None
     if dom is not None:
         if use_graph:
@@ -405,7 +456,7 @@ def main():
                               f, indent=1)
         else:
             result["roofline"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if want_cpu:
             result["cpu_baseline"] = cpu_baseline(sd_cpu, args.cpu_seconds)
         print(json.dumps(result), flush=True)
     if world > 1:

@@ -1,6 +1,6 @@
 """HBM traffic and MFMA busy of several kernels of the training step, from unfiltered rocprofv3 PMC
 passes over bench.py's eager steps, each against the census's algorithmic bytes / FLOPs for the same
-launches (bench.py --table-out). Writes <out_prefix>_<tag>.json per kernel and, for the step's
+launches (bench.py --full --table-out). Writes <out_prefix>_<tag>.json per kernel and, for the step's
 measured-dominant kernel (first table row), <out_prefix>_dominant.json (read by bench.py).
 
   rocprofv3 --pmc FETCH_SIZE -d <fetch_dir> -- python3 bench.py --eager ...          (one pass each)
