@@ -1056,186 +1056,104 @@ __global__ void head_repack4_kernel(int n4, int heads, int q4s, int ls4, int q4d
 }
 
 unsigned grid_for(long n) { return (unsigned)min((long)8192, max(1L, (n + 255) / 256)); }
-
-// f16: the 16-bit lambda is generic over its storage type (bf16_t or f16_t)
-template <typename F16, typename F32>
-int dispatch(int dtype, F16 f16, F32 f32) {
-  if (dtype == DFM_BF16) return f16(bf16_t{});
-  if (dtype == DFM_F16) return f16(f16_t{});
-  if (dtype == DFM_F32) return f32();
-  dfm_set_error("attention: bad dtype");
-  return DFM_ERR_DTYPE;
-}
 }  // namespace
 
 extern "C" int dfm_adaptive_pool7_fwd(int dtype, int B, int H, int W, int C, const void* x, long ldx, void* y,
                                       long ldy, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   hipStream_t s = (hipStream_t)stream;
   if (C <= 2048 && vec_ok(C, x, ldx)) {
     const size_t lds = (size_t)(256 / (C / 8)) * C * sizeof(float);
-    return dispatch(
-        dtype,
-        [&](auto tag16) {
-        using T16 = decltype(tag16);
-          DFM_LAUNCH(pool7_fwd_vec_kernel<T16>, dim3(B * 49), dim3(256), lds, s, B, H, W, C,
-                             (const T16*)x, ldx, (T16*)y, ldy);
-          DFM_LAUNCH_CHECK();
-          return DFM_OK;
-        },
-        [&] {
-          DFM_LAUNCH(pool7_fwd_vec_kernel<float>, dim3(B * 49), dim3(256), lds, s, B, H, W, C,
-                             (const float*)x, ldx, (float*)y, ldy);
-          DFM_LAUNCH_CHECK();
-          return DFM_OK;
-        });
+    DFM_DTYPE_SWITCH(dtype, T,
+                     DFM_LAUNCH(pool7_fwd_vec_kernel<T>, dim3(B * 49), dim3(256), lds, s, B, H, W, C, (const T*)x, ldx,
+                                (T*)y, ldy));
+  } else {
+    dim3 grid(B * 49, cdiv(C, 256));
+    DFM_DTYPE_SWITCH(dtype, T,
+                     DFM_LAUNCH(pool7_fwd_kernel<T>, grid, dim3(256), 0, s, B, H, W, C, (const T*)x, ldx, (T*)y, ldy));
   }
-  dim3 grid(B * 49, cdiv(C, 256));
-  return dispatch(
-      dtype,
-      [&](auto tag16) {
-        using T16 = decltype(tag16);
-        DFM_LAUNCH(pool7_fwd_kernel<T16>, grid, dim3(256), 0, s, B, H, W, C, (const T16*)x, ldx, (T16*)y, ldy);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      },
-      [&] {
-        DFM_LAUNCH(pool7_fwd_kernel<float>, grid, dim3(256), 0, s, B, H, W, C, (const float*)x, ldx, (float*)y, ldy);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      });
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
 }
 
 extern "C" int dfm_adaptive_pool7_bwd(int dtype, int B, int H, int W, int C, const void* dy, long lddy, void* dx,
                                       long lddx, int accumulate, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   hipStream_t s = (hipStream_t)stream;
   if (vec_ok(C, dy, lddy) && vec_ok(C, dx, lddx)) {
     const unsigned gv = grid_for((long)B * H * W * (C / 8));
-    return dispatch(
-        dtype,
-        [&](auto tag16) {
-        using T16 = decltype(tag16);
-          DFM_LAUNCH(pool7_bwd_vec_kernel<T16>, dim3(gv), dim3(256), 0, s, B, H, W, C, (const T16*)dy,
-                             lddy, (T16*)dx, lddx, accumulate);
-          DFM_LAUNCH_CHECK();
-          return DFM_OK;
-        },
-        [&] {
-          DFM_LAUNCH(pool7_bwd_vec_kernel<float>, dim3(gv), dim3(256), 0, s, B, H, W, C, (const float*)dy,
-                             lddy, (float*)dx, lddx, accumulate);
-          DFM_LAUNCH_CHECK();
-          return DFM_OK;
-        });
+    DFM_DTYPE_SWITCH(dtype, T,
+                     DFM_LAUNCH(pool7_bwd_vec_kernel<T>, dim3(gv), dim3(256), 0, s, B, H, W, C, (const T*)dy, lddy,
+                                (T*)dx, lddx, accumulate));
+  } else {
+    const unsigned g = grid_for((long)B * H * W * C);
+    DFM_DTYPE_SWITCH(dtype, T,
+                     DFM_LAUNCH(pool7_bwd_kernel<T>, dim3(g), dim3(256), 0, s, B, H, W, C, (const T*)dy, lddy, (T*)dx,
+                                lddx, accumulate));
   }
-  const unsigned g = grid_for((long)B * H * W * C);
-  return dispatch(
-      dtype,
-      [&](auto tag16) {
-        using T16 = decltype(tag16);
-        DFM_LAUNCH(pool7_bwd_kernel<T16>, dim3(g), dim3(256), 0, s, B, H, W, C, (const T16*)dy, lddy, (T16*)dx, lddx, accumulate);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      },
-      [&] {
-        DFM_LAUNCH(pool7_bwd_kernel<float>, dim3(g), dim3(256), 0, s, B, H, W, C, (const float*)dy, lddy, (float*)dx, lddx, accumulate);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      });
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
 }
 
 extern "C" int dfm_bilinear_fwd(int dtype, int B, int Hi, int Wi, int Ho, int Wo, int C, const void* x, long ldx,
                                 void* y, long ldy, int accumulate, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   hipStream_t s = (hipStream_t)stream;
   if (vec_ok(C, x, ldx) && vec_ok(C, y, ldy)) {
     const unsigned gv = grid_for((long)B * Ho * Wo * (C / 8));
-    return dispatch(
-        dtype,
-        [&](auto tag16) {
-        using T16 = decltype(tag16);
-          DFM_LAUNCH(bilinear_fwd_vec_kernel<T16>, dim3(gv), dim3(256), 0, s, B, Hi, Wi, Ho, Wo, C,
-                             (const T16*)x, ldx, (T16*)y, ldy, accumulate);
-          DFM_LAUNCH_CHECK();
-          return DFM_OK;
-        },
-        [&] {
-          DFM_LAUNCH(bilinear_fwd_vec_kernel<float>, dim3(gv), dim3(256), 0, s, B, Hi, Wi, Ho, Wo, C,
-                             (const float*)x, ldx, (float*)y, ldy, accumulate);
-          DFM_LAUNCH_CHECK();
-          return DFM_OK;
-        });
+    DFM_DTYPE_SWITCH(dtype, T,
+                     DFM_LAUNCH(bilinear_fwd_vec_kernel<T>, dim3(gv), dim3(256), 0, s, B, Hi, Wi, Ho, Wo, C,
+                                (const T*)x, ldx, (T*)y, ldy, accumulate));
+  } else {
+    const unsigned g = grid_for((long)B * Ho * Wo * C);
+    DFM_DTYPE_SWITCH(dtype, T,
+                     DFM_LAUNCH(bilinear_fwd_kernel<T>, dim3(g), dim3(256), 0, s, B, Hi, Wi, Ho, Wo, C, (const T*)x, ldx,
+                                (T*)y, ldy, accumulate));
   }
-  const unsigned g = grid_for((long)B * Ho * Wo * C);
-  return dispatch(
-      dtype,
-      [&](auto tag16) {
-        using T16 = decltype(tag16);
-        DFM_LAUNCH(bilinear_fwd_kernel<T16>, dim3(g), dim3(256), 0, s, B, Hi, Wi, Ho, Wo, C, (const T16*)x, ldx, (T16*)y, ldy, accumulate);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      },
-      [&] {
-        DFM_LAUNCH(bilinear_fwd_kernel<float>, dim3(g), dim3(256), 0, s, B, Hi, Wi, Ho, Wo, C, (const float*)x, ldx, (float*)y, ldy, accumulate);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      });
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
 }
 
 extern "C" int dfm_bilinear_bwd(int dtype, int B, int Hi, int Wi, int Ho, int Wo, int C, const void* dy, long lddy,
                                 void* dx, long lddx, int accumulate, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   hipStream_t s = (hipStream_t)stream;
   // taps per axis: ~2 * out/in + 3 must fit the block's LDS lists
   const bool taps_fit = 2 * (Ho / Hi) + 6 <= BL_MAXT && 2 * (Wo / Wi) + 6 <= BL_MAXT && Ho >= Hi && Wo >= Wi;
   if (C <= 2048 && taps_fit && vec_ok(C, dy, lddy) && (uintptr_t)dx % 4 == 0) {
     const size_t lds = (size_t)(256 / (C / 8)) * C * sizeof(float);
-    return dispatch(
-        dtype,
-        [&](auto tag16) {
-        using T16 = decltype(tag16);
-          DFM_LAUNCH(bilinear_bwd_vec_kernel<T16>, dim3(B * Hi * Wi), dim3(256), lds, s, B, Hi, Wi, Ho, Wo,
-                             C, (const T16*)dy, lddy, (T16*)dx, lddx, accumulate);
-          DFM_LAUNCH_CHECK();
-          return DFM_OK;
-        },
-        [&] {
-          DFM_LAUNCH(bilinear_bwd_vec_kernel<float>, dim3(B * Hi * Wi), dim3(256), lds, s, B, Hi, Wi, Ho, Wo,
-                             C, (const float*)dy, lddy, (float*)dx, lddx, accumulate);
-          DFM_LAUNCH_CHECK();
-          return DFM_OK;
-        });
+    DFM_DTYPE_SWITCH(dtype, T,
+                     DFM_LAUNCH(bilinear_bwd_vec_kernel<T>, dim3(B * Hi * Wi), dim3(256), lds, s, B, Hi, Wi, Ho, Wo, C,
+                                (const T*)dy, lddy, (T*)dx, lddx, accumulate));
+  } else {
+    const unsigned g = grid_for((long)B * Hi * Wi * C);
+    DFM_DTYPE_SWITCH(dtype, T,
+                     DFM_LAUNCH(bilinear_bwd_kernel<T>, dim3(g), dim3(256), 0, s, B, Hi, Wi, Ho, Wo, C, (const T*)dy,
+                                lddy, (T*)dx, lddx, accumulate));
   }
-  const unsigned g = grid_for((long)B * Hi * Wi * C);
-  return dispatch(
-      dtype,
-      [&](auto tag16) {
-        using T16 = decltype(tag16);
-        DFM_LAUNCH(bilinear_bwd_kernel<T16>, dim3(g), dim3(256), 0, s, B, Hi, Wi, Ho, Wo, C, (const T16*)dy, lddy, (T16*)dx, lddx, accumulate);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      },
-      [&] {
-        DFM_LAUNCH(bilinear_bwd_kernel<float>, dim3(g), dim3(256), 0, s, B, Hi, Wi, Ho, Wo, C, (const float*)dy, lddy, (float*)dx, lddx, accumulate);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      });
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
 }
 
 static int nchunks(int N) { return (N + NC - 1) / NC; }
 
-// bf16 MFMA path: head dim a multiple of 16 (<= 48), 16-byte aligned rows
+// 16-bit MFMA path: head dim a multiple of 16 (<= 48), 16-byte aligned rows
 static bool attn_mfma_ok(int dtype, int dh, const void* const* ptrs, const long* lds, int n) {
-  if ((dtype != DFM_BF16 && dtype != DFM_F16) || !(dh == 16 || dh == 32 || dh == 48)) return false;
+  if (dfm_dtype_size(dtype) != 2 || !(dh == 16 || dh == 32 || dh == 48)) return false;
   for (int i = 0; i < n; ++i)
     if ((uintptr_t)ptrs[i] % 16 != 0 || lds[i] % 8 != 0) return false;
   return true;
 }
-// Other bf16 head dims below 48 (DFormer-Large: 576 / 16 heads = 36 in stages 2-3) run the same
+// Other 16-bit head dims below 48 (DFormer-Large: 576 / 16 heads = 36 in stages 2-3) run the same
 // MFMA kernels on head slices zero-padded to the next multiple of 16 in the workspace: padded
 // dims add 0 to Q K^T and produce 0 output columns, which the unpack drops.
 static int attn_pad_dh(int dtype, int dh) {
-  if ((dtype != DFM_BF16 && dtype != DFM_F16) || dh % 16 == 0 || dh > 48) return 0;
+  if (dfm_dtype_size(dtype) != 2 || dh % 16 == 0 || dh > 48) return 0;
   return (dh + 15) / 16 * 16;
 }
 static int attn_kpw(int N) { return N >= 2048 ? 128 : 64; }  // keys per wave (a multiple of 32 and of NC)
 
+// the 16-bit MFMA kernels (T = bf16_t / f16_t storage) and their combine / dQ-reduce kernels
 template <typename T, int DH>
 static void attn_mfma_launch(AttnArgs& a, bool bwd, hipStream_t s) {
   const int kpw = attn_kpw(a.N);
@@ -1245,25 +1163,20 @@ static void attn_mfma_launch(AttnArgs& a, bool bwd, hipStream_t s) {
   else DFM_LAUNCH((attn_fwd_mfma_kernel<T, DH>), grid, dim3(256), 0, s, a, kpw, groups);
 }
 template <typename T>
-static void attn_mfma_t(AttnArgs& a, bool bwd, hipStream_t s) {
+static void attn_mfma(AttnArgs& a, bool bwd, hipStream_t s) {
   if (a.dh == 16) attn_mfma_launch<T, 16>(a, bwd, s);
   else if (a.dh == 32) attn_mfma_launch<T, 32>(a, bwd, s);
   else attn_mfma_launch<T, 48>(a, bwd, s);
 }
-// the 16-bit MFMA kernels (bf16 / f16 storage) and their combine / dQ-reduce kernels
-static void attn_mfma(int dtype, AttnArgs& a, bool bwd, hipStream_t s) {
-  if (dtype == DFM_F16) attn_mfma_t<f16_t>(a, bwd, s);
-  else attn_mfma_t<bf16_t>(a, bwd, s);
-}
-static void attn_combine16(int dtype, AttnArgs& a, hipStream_t s) {
+template <typename T>
+static void attn_combine16(AttnArgs& a, hipStream_t s) {
   const dim3 g(cdiv((long)a.B * a.heads * NQ * (a.dh / 4), 256));
-  if (dtype == DFM_F16) DFM_LAUNCH(attn_fwd_combine_v4_kernel<f16_t>, g, dim3(256), 0, s, a);
-  else DFM_LAUNCH(attn_fwd_combine_v4_kernel<bf16_t>, g, dim3(256), 0, s, a);
+  DFM_LAUNCH(attn_fwd_combine_v4_kernel<T>, g, dim3(256), 0, s, a);
 }
-static void attn_dq_reduce16(int dtype, AttnArgs& a, hipStream_t s) {
+template <typename T>
+static void attn_dq_reduce16(AttnArgs& a, hipStream_t s) {
   const dim3 g(cdiv((long)a.B * a.heads * NQ * (a.dh / 4), 256));
-  if (dtype == DFM_F16) DFM_LAUNCH(attn_dq_reduce_v4_kernel<f16_t>, g, dim3(256), 0, s, a);
-  else DFM_LAUNCH(attn_dq_reduce_v4_kernel<bf16_t>, g, dim3(256), 0, s, a);
+  DFM_LAUNCH(attn_dq_reduce_v4_kernel<T>, g, dim3(256), 0, s, a);
 }
 
 static size_t attn_partials_bytes(int B, int heads, int N, int dh) {
@@ -1296,6 +1209,7 @@ static void head_repack(long rows, int heads, int dsrc, long lds, int ddst, long
 extern "C" int dfm_pooled_attn_fwd(int dtype, int B, int heads, int N, int dh, const void* q, long ldq, const void* k,
                                    const void* v, long ldkv, float scale, void* o, long ldo, float* lse,
                                    void* workspace, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(q && k && v && o && lse && workspace && N > 0 && dh > 0 && dh <= 64, "dfm_pooled_attn_fwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
   AttnArgs a{};
@@ -1313,9 +1227,11 @@ extern "C" int dfm_pooled_attn_fwd(int dtype, int B, int heads, int N, int dh, c
     head_repack((long)B * N, heads, dh, ldkv, dp, ldp, v, pv, s);
     a.dh = dp; a.q = pq; a.ldq = ldp; a.k = pk; a.v = pv; a.ldkv = ldp; a.o = po; a.ldo = ldp;
     a.nchunk = (N + attn_kpw(N) - 1) / attn_kpw(N);
-    attn_mfma(dtype, a, false, s);
-    a.nchunk = (a.nchunk + 3) / 4;  // one merged partial per block (chunk group)
-    attn_combine16(dtype, a, s);
+    DFM_DTYPE_SWITCH16(dtype, T, {
+      attn_mfma<T>(a, false, s);
+      a.nchunk = (a.nchunk + 3) / 4;  // one merged partial per block (chunk group)
+      attn_combine16<T>(a, s);
+    });
     head_repack((long)B * NQ, heads, dp, ldp, dh, ldo, po, o, s);
     DFM_LAUNCH_CHECK();
     return DFM_OK;
@@ -1325,10 +1241,12 @@ extern "C" int dfm_pooled_attn_fwd(int dtype, int B, int heads, int N, int dh, c
     const long lds_[] = {ldq, ldkv, ldkv, ldo};
     if (attn_mfma_ok(dtype, dh, ptrs, lds_, 4)) {
       a.nchunk = (N + attn_kpw(N) - 1) / attn_kpw(N);
-      attn_mfma(dtype, a, false, s);
-      DFM_LAUNCH_CHECK();
-      a.nchunk = (a.nchunk + 3) / 4;  // one merged partial per block (chunk group)
-      attn_combine16(dtype, a, s);
+      DFM_DTYPE_SWITCH16(dtype, T, {
+        attn_mfma<T>(a, false, s);
+        DFM_LAUNCH_CHECK();
+        a.nchunk = (a.nchunk + 3) / 4;  // one merged partial per block (chunk group)
+        attn_combine16<T>(a, s);
+      });
       DFM_LAUNCH_CHECK();
       return DFM_OK;
     }
@@ -1337,29 +1255,20 @@ extern "C" int dfm_pooled_attn_fwd(int dtype, int B, int heads, int N, int dh, c
   const size_t lds = (size_t)(NQ * DP + 2 * NC * DP + NQ * (NC + 1)) * sizeof(float);
   const unsigned nblk = B * heads * a.nchunk;
   const unsigned g = grid_for((long)B * heads * NQ * dh);
-  return dispatch(
-      dtype,
-      [&](auto tag16) {
-        using T16 = decltype(tag16);
-        DFM_LAUNCH(attn_fwd_chunk_kernel<T16>, dim3(nblk), dim3(256), lds, s, a);
-        DFM_LAUNCH_CHECK();
-        DFM_LAUNCH(attn_fwd_combine_kernel<T16>, dim3(g), dim3(256), 0, s, a);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      },
-      [&] {
-        DFM_LAUNCH(attn_fwd_chunk_kernel<float>, dim3(nblk), dim3(256), lds, s, a);
-        DFM_LAUNCH_CHECK();
-        DFM_LAUNCH(attn_fwd_combine_kernel<float>, dim3(g), dim3(256), 0, s, a);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      });
+  DFM_DTYPE_SWITCH(dtype, T, {
+    DFM_LAUNCH(attn_fwd_chunk_kernel<T>, dim3(nblk), dim3(256), lds, s, a);
+    DFM_LAUNCH_CHECK();
+    DFM_LAUNCH(attn_fwd_combine_kernel<T>, dim3(g), dim3(256), 0, s, a);
+  });
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
 }
 
 extern "C" int dfm_pooled_attn_bwd(int dtype, int B, int heads, int N, int dh, const void* q, long ldq, const void* k,
                                    const void* v, long ldkv, float scale, const void* o, long ldo, const void* dout,
                                    long lddo, const float* lse, void* dq, void* dk, void* dv, long lddkv,
                                    void* workspace, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(q && k && v && o && dout && lse && dq && dk && dv && workspace && dh <= 64,
                 "dfm_pooled_attn_bwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
@@ -1387,8 +1296,10 @@ extern "C" int dfm_pooled_attn_bwd(int dtype, int B, int heads, int N, int dh, c
     a.dh = dp; a.q = pq; a.ldq = ldp; a.k = pk; a.v = pv; a.ldkv = ldp; a.o = po; a.ldo = ldp;
     a.dout = pdo; a.lddo = ldp; a.dq = pdq; a.dk = pdk; a.dv = pdv; a.lddkv = ldp;
     a.nchunk = (N + attn_kpw(N) - 1) / attn_kpw(N);
-    attn_mfma(dtype, a, true, s);
-    attn_dq_reduce16(dtype, a, s);
+    DFM_DTYPE_SWITCH16(dtype, T, {
+      attn_mfma<T>(a, true, s);
+      attn_dq_reduce16<T>(a, s);
+    });
     head_repack((long)B * NQ, heads, dp, ldp, dh, ldq, pdq, dq, s);
     head_repack((long)B * N, heads, dp, ldp, dh, lddkv, pdk, dk, s);
     head_repack((long)B * N, heads, dp, ldp, dh, lddkv, pdv, dv, s);
@@ -1400,9 +1311,11 @@ extern "C" int dfm_pooled_attn_bwd(int dtype, int B, int heads, int N, int dh, c
     const long lds_[] = {ldq, ldkv, ldkv, ldo, lddo, ldq, lddkv, lddkv};
     if (attn_mfma_ok(dtype, dh, ptrs, lds_, 8)) {
       a.nchunk = (N + attn_kpw(N) - 1) / attn_kpw(N);
-      attn_mfma(dtype, a, true, s);
-      DFM_LAUNCH_CHECK();
-      attn_dq_reduce16(dtype, a, s);
+      DFM_DTYPE_SWITCH16(dtype, T, {
+        attn_mfma<T>(a, true, s);
+        DFM_LAUNCH_CHECK();
+        attn_dq_reduce16<T>(a, s);
+      });
       DFM_LAUNCH_CHECK();
       return DFM_OK;
     }
@@ -1411,21 +1324,11 @@ extern "C" int dfm_pooled_attn_bwd(int dtype, int B, int heads, int N, int dh, c
   const size_t lds = (size_t)(2 * NQ * DP + 2 * NC * DP + NQ * (NC + 1) + 2 * NQ) * sizeof(float);
   const unsigned nblk = B * heads * a.nchunk;
   const unsigned g = grid_for((long)B * heads * NQ * dh);
-  return dispatch(
-      dtype,
-      [&](auto tag16) {
-        using T16 = decltype(tag16);
-        DFM_LAUNCH(attn_bwd_chunk_kernel<T16>, dim3(nblk), dim3(256), lds, s, a);
-        DFM_LAUNCH_CHECK();
-        DFM_LAUNCH(attn_dq_reduce_kernel<T16>, dim3(g), dim3(256), 0, s, a);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      },
-      [&] {
-        DFM_LAUNCH(attn_bwd_chunk_kernel<float>, dim3(nblk), dim3(256), lds, s, a);
-        DFM_LAUNCH_CHECK();
-        DFM_LAUNCH(attn_dq_reduce_kernel<float>, dim3(g), dim3(256), 0, s, a);
-        DFM_LAUNCH_CHECK();
-        return DFM_OK;
-      });
+  DFM_DTYPE_SWITCH(dtype, T, {
+    DFM_LAUNCH(attn_bwd_chunk_kernel<T>, dim3(nblk), dim3(256), lds, s, a);
+    DFM_LAUNCH_CHECK();
+    DFM_LAUNCH(attn_dq_reduce_kernel<T>, dim3(g), dim3(256), 0, s, a);
+  });
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
 }

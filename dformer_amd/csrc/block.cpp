@@ -17,6 +17,7 @@
 #include "../../include/dformer_hip.h"
 
 void dfm_set_error(const char* fmt, ...);
+static size_t dtype_size(int dtype) { return dtype == DFM_F32 ? 4 : 2; }  // as common.h's dfm_dtype_size
 
 namespace {
 
@@ -54,7 +55,7 @@ struct Run {
   size_t scratch_cap = 0;
   int err = DFM_OK;
 
-  Run(int dtype, bool planning, hipStream_t st) : dt(dtype), es(dtype == DFM_F32 ? 4 : 2), s(st), plan(planning) {}
+  Run(int dtype, bool planning, hipStream_t st) : dt(dtype), es(dtype_size(dtype)), s(st), plan(planning) {}
   V act(long rows, long cols, Arena& a) { return V{a.take((size_t)rows * cols * es), cols, es}; }
   V keep(long rows, long cols) { return act(rows, cols, saved); }
   V temp(long rows, long cols) { return act(rows, cols, tmp); }
@@ -613,7 +614,7 @@ void block_sizes(int dtype, const DfmBlockDesc* d, size_t* saved, size_t* ws) {
   static float* const gnone[DFM_BLOCK_NPARAM] = {};
   const void* none[DFM_BLOCK_NPARAM] = {};
   const void* stacked[DFM_BLOCK_NPARAM] = {};
-  const size_t es = dtype == DFM_F32 ? 4 : 2;
+  const size_t es = dtype_size(dtype);
   char* const w0 = reinterpret_cast<char*>(size_t(1) << 40);
   char* const b0 = reinterpret_cast<char*>(size_t(1) << 41);
   char* const p0 = reinterpret_cast<char*>(size_t(1) << 42);
@@ -662,6 +663,10 @@ int block_call(bool fwd, int dtype, const DfmBlockDesc* d, const void* const* pa
                const void* dye, void* dx, void* dxe, float* const* grads, void* workspace, size_t workspace_bytes,
                hipStream_t s) {
   const char* who = fwd ? "dfm_block_fwd" : "dfm_block_bwd";
+  if (dtype != DFM_F32 && dtype != DFM_BF16 && dtype != DFM_F16) {
+    dfm_set_error("%s: unsupported dtype %d", who, dtype);
+    return DFM_ERR_DTYPE;
+  }
   if (!desc_ok(dtype, d) || !params || !x || !xe) {
     dfm_set_error("%s: bad descriptor / dtype %d or null argument", who, dtype);
     return DFM_ERR_ARG;

@@ -227,22 +227,43 @@ template <> DFM_INLINE bf16x8_t pack16x8<f16_t>(const float* v) {
   return __builtin_bit_cast(bf16x8_t, make_uint4(w[0], w[1], w[2], w[3]));
 }
 
-// Dispatch a 16-bit-or-float32 body on the dtype code: F(T{}) with T = float, bf16_t or f16_t.
-#define DFM_DTYPE_SWITCH(dtype, T, ...)                      \
-  [&]() -> int {                                             \
-    if ((dtype) == DFM_BF16) {                               \
-      using T = bf16_t;                                      \
-      return __VA_ARGS__;                                    \
-    } else if ((dtype) == DFM_F16) {                         \
-      using T = f16_t;                                       \
-      return __VA_ARGS__;                                    \
-    } else if ((dtype) == DFM_F32) {                         \
-      using T = float;                                       \
-      return __VA_ARGS__;                                    \
-    }                                                        \
-    dfm_set_error("%s: unsupported dtype %d", __func__, (int)(dtype)); \
-    return DFM_ERR_DTYPE;                                    \
-  }()
+// ---- dtype dispatch: the one place a dtype code selects a storage type.
+// DFM_DTYPE_SWITCH(dtype, T, stmt) runs `stmt` with T = bf16_t, f16_t or float (a launch, or `return
+// typed<T>(...)`); DFM_DTYPE_SWITCH16 is the same for the 16-bit-only paths (bf16_t / f16_t). Any other
+// code makes the enclosing function return DFM_ERR_DTYPE with "<function>: unsupported dtype <code>".
+// They are statements of the calling function (no lambda), so __func__, DFM_CHECK_ARG and
+// DFM_LAUNCH_CHECK inside `stmt` name and leave that function.
+// An entry point rejects an unknown code before any other work: DFM_CHECK_DTYPE(dtype) (or the 16-bit
+// DFM_CHECK_DTYPE16) as its first line.
+void dfm_set_error(const char* fmt, ...);
+static inline int dfm_dtype_error(const char* func, int dtype) {
+  dfm_set_error("%s: unsupported dtype %d", func, dtype);
+  return DFM_ERR_DTYPE;
+}
+static inline int dfm_dtype_size(int dtype) { return dtype == DFM_F32 ? 4 : 2; }  // bytes per element
+#define DFM_DTYPE_SWITCH16(dtype, T, ...)             \
+  do {                                                \
+    if ((dtype) == DFM_BF16) {                        \
+      using T = bf16_t;                               \
+      __VA_ARGS__;                                    \
+    } else if ((dtype) == DFM_F16) {                  \
+      using T = f16_t;                                \
+      __VA_ARGS__;                                    \
+    } else {                                          \
+      return dfm_dtype_error(__func__, (int)(dtype)); \
+    }                                                 \
+  } while (0)
+#define DFM_DTYPE_SWITCH(dtype, T, ...)               \
+  do {                                                \
+    if ((dtype) == DFM_F32) {                         \
+      using T = float;                                \
+      __VA_ARGS__;                                    \
+    } else {                                          \
+      DFM_DTYPE_SWITCH16(dtype, T, __VA_ARGS__);      \
+    }                                                 \
+  } while (0)
+#define DFM_CHECK_DTYPE(dtype) DFM_DTYPE_SWITCH(dtype, DfmT_, (void)0)
+#define DFM_CHECK_DTYPE16(dtype) DFM_DTYPE_SWITCH16(dtype, DfmT_, (void)0)
 
 // ---- second stage of the deterministic two-stage column reductions:
 // out[e] (+)= sum_{b < nblk} part[b * n + e], fixed summation order; 64 columns x 16 row-lanes
@@ -309,8 +330,7 @@ void dfm_trace_post(const void* func, hipStream_t s);
     if (_dfm_tr) dfm_trace_post((const void*)(kern), (hipStream_t)(stream)); \
   } while (0)
 
-// ---- host-side error plumbing (thread-local last error string)
-void dfm_set_error(const char* fmt, ...);
+// ---- host-side error plumbing (thread-local last error string; dfm_set_error is declared above)
 #define DFM_CHECK_ARG(cond, ...)          \
   do {                                    \
     if (!(cond)) {                        \

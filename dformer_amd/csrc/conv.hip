@@ -275,6 +275,8 @@ extern "C" int dfm_conv3s2_im2col(int dtype_in, int dtype_out, int B, int H, int
                                   long sh, long sw, const void* x, const float* mean, const float* rstd,
                                   const float* gamma, const float* beta, int gelu, int Kp, void* cols,
                                   dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype_in);
+  DFM_CHECK_DTYPE(dtype_out);
   DFM_CHECK_ARG(x && cols, "dfm_conv3s2_im2col: null argument");
   DFM_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0, "dfm_conv3s2_im2col: bad shape");
   DFM_CHECK_ARG(Kp % 8 == 0 && Kp >= 9 * Cin, "dfm_conv3s2_im2col: Kp=%d must be a multiple of 8 >= 9*Cin", Kp);
@@ -283,6 +285,7 @@ extern "C" int dfm_conv3s2_im2col(int dtype_in, int dtype_out, int B, int H, int
   DFM_CHECK_ARG(!mean || Cin <= kMaxAffC, "dfm_conv3s2_im2col: folded BN over %d > %d channels", Cin, kMaxAffC);
   const Affine af{mean, rstd, gamma, beta, gelu};
   hipStream_t s = (hipStream_t)stream;
+  // the instantiated (in, out) pairs, as an explicit table
   if (dtype_in == DFM_F32 && dtype_out == DFM_F32)
     return im2col_typed<float, float>(B, H, W, Cin, sb, sc, sh, sw, x, af, Kp, cols, s);
   if (dtype_in == DFM_F32 && dtype_out == DFM_BF16)
@@ -295,7 +298,7 @@ extern "C" int dfm_conv3s2_im2col(int dtype_in, int dtype_out, int B, int H, int
     return im2col_typed<float, f16_t>(B, H, W, Cin, sb, sc, sh, sw, x, af, Kp, cols, s);
   if (dtype_in == DFM_F16 && dtype_out == DFM_F16)
     return im2col_typed<f16_t, f16_t>(B, H, W, Cin, sb, sc, sh, sw, x, af, Kp, cols, s);
-  dfm_set_error("dfm_conv3s2_im2col: unsupported dtypes %d -> %d", dtype_in, dtype_out);
+  dfm_set_error("dfm_conv3s2_im2col: unsupported dtype %d -> %d", dtype_in, dtype_out);
   return DFM_ERR_DTYPE;
 }
 
@@ -303,6 +306,7 @@ extern "C" int dfm_conv3s2_col2im(int dtype, int B, int H, int W, int Cin, const
                                   const void* x, long ldx, const float* mean, const float* rstd, const float* gamma,
                                   const float* beta, int gelu, void* dx, long lddx, int accumulate,
                                   dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(dcols && dx && (!gelu || x), "dfm_conv3s2_col2im: null argument");
   DFM_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0 && Cin % 8 == 0, "dfm_conv3s2_col2im: Cin=%d must be a multiple of 8",
                 Cin);
@@ -320,16 +324,9 @@ extern "C" int dfm_conv3s2_col2im(int dtype, int B, int H, int W, int Cin, const
   DFM_LAUNCH((col2im_vec_kernel<T, I>), dim3(grid_for(n)), dim3(kThreads), 0, s, B, H, W, Cin, Ho, Wo,        \
              (const T*)dcols, ldc, (const T*)x, ldx, af, (T*)dx, lddx, accumulate)
   const bool i32 = n < (1L << 31);
-  if (dtype == DFM_BF16) {
-    if (i32) DFM_C2IV(bf16_t, unsigned); else DFM_C2IV(bf16_t, long);
-  } else if (dtype == DFM_F16) {
-    if (i32) DFM_C2IV(f16_t, unsigned); else DFM_C2IV(f16_t, long);
-  } else if (dtype == DFM_F32) {
-    if (i32) DFM_C2IV(float, unsigned); else DFM_C2IV(float, long);
-  } else {
-    dfm_set_error("dfm_conv3s2_col2im: unsupported dtype %d", dtype);
-    return DFM_ERR_DTYPE;
-  }
+  DFM_DTYPE_SWITCH(dtype, T, {
+    if (i32) DFM_C2IV(T, unsigned); else DFM_C2IV(T, long);
+  });
 #undef DFM_C2IV
   DFM_LAUNCH_CHECK();
   return DFM_OK;
@@ -337,6 +334,8 @@ extern "C" int dfm_conv3s2_col2im(int dtype, int B, int H, int W, int Cin, const
 
 extern "C" int dfm_conv3s2_col2im_nchw(int dtype, int dtype_out, int B, int H, int W, int Cin, const void* dcols,
                                        long ldc, void* dx, long sb, long sc, long sh, long sw, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  DFM_CHECK_DTYPE(dtype_out);
   DFM_CHECK_ARG(dcols && dx && B > 0 && H > 0 && W > 0 && Cin > 0 && ldc >= 9 * Cin,
                 "dfm_conv3s2_col2im_nchw: bad argument");
   hipStream_t s = (hipStream_t)stream;
@@ -345,6 +344,7 @@ extern "C" int dfm_conv3s2_col2im_nchw(int dtype, int dtype_out, int B, int H, i
 #define DFM_C2I(T, TO)                                                                                        \
   DFM_LAUNCH((col2im_gen_kernel<T, TO>), dim3(grid_for(n)), dim3(kThreads), 0, s, B, Cin, H, W, Ho, Wo,       \
              (const T*)dcols, ldc, (TO*)dx, sb, sc, sh, sw)
+  // the instantiated (in, out) pairs, as an explicit table
   if (dtype == DFM_F32 && dtype_out == DFM_F32) DFM_C2I(float, float);
   else if (dtype == DFM_BF16 && dtype_out == DFM_F32) DFM_C2I(bf16_t, float);
   else if (dtype == DFM_BF16 && dtype_out == DFM_BF16) DFM_C2I(bf16_t, bf16_t);
@@ -352,7 +352,7 @@ extern "C" int dfm_conv3s2_col2im_nchw(int dtype, int dtype_out, int B, int H, i
   else if (dtype == DFM_F16 && dtype_out == DFM_F16) DFM_C2I(f16_t, f16_t);
   else if (dtype == DFM_F32 && dtype_out == DFM_BF16) DFM_C2I(float, bf16_t);
   else {
-    dfm_set_error("dfm_conv3s2_col2im_nchw: unsupported dtypes %d -> %d", dtype, dtype_out);
+    dfm_set_error("dfm_conv3s2_col2im_nchw: unsupported dtype %d -> %d", dtype, dtype_out);
     return DFM_ERR_DTYPE;
   }
 #undef DFM_C2I
@@ -362,20 +362,13 @@ extern "C" int dfm_conv3s2_col2im_nchw(int dtype, int dtype_out, int B, int H, i
 
 extern "C" int dfm_conv3_weight_pack(int dtype_out, int Cout, int Cin, int Kp, const float* w, void* wp,
                                      dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype_out);
   DFM_CHECK_ARG(w && wp, "dfm_conv3_weight_pack: null argument");
   DFM_CHECK_ARG(Cout > 0 && Cin > 0 && Kp >= 9 * Cin, "dfm_conv3_weight_pack: bad shape");
   hipStream_t s = (hipStream_t)stream;
   const long n = (long)Cout * Kp;
-  if (dtype_out == DFM_BF16)
-    DFM_LAUNCH(weight_pack_kernel<bf16_t>, dim3(grid_for(n)), dim3(kThreads), 0, s, Cout, Cin, Kp, w, (bf16_t*)wp);
-  else if (dtype_out == DFM_F16)
-    DFM_LAUNCH(weight_pack_kernel<f16_t>, dim3(grid_for(n)), dim3(kThreads), 0, s, Cout, Cin, Kp, w, (f16_t*)wp);
-  else if (dtype_out == DFM_F32)
-    DFM_LAUNCH(weight_pack_kernel<float>, dim3(grid_for(n)), dim3(kThreads), 0, s, Cout, Cin, Kp, w, (float*)wp);
-  else {
-    dfm_set_error("dfm_conv3_weight_pack: unsupported dtype %d", dtype_out);
-    return DFM_ERR_DTYPE;
-  }
+  DFM_DTYPE_SWITCH(dtype_out, T,
+                   DFM_LAUNCH(weight_pack_kernel<T>, dim3(grid_for(n)), dim3(kThreads), 0, s, Cout, Cin, Kp, w, (T*)wp));
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }

@@ -853,7 +853,7 @@ DfmGemmDesc w1_desc(const DfmConvFFNDesc* d) {
 }
 
 BwdWs bwd_ws(int dtype, const DfmConvFFNDesc* d) {
-  const size_t es = dtype == DFM_F32 ? 4 : 2;
+  const size_t es = dfm_dtype_size(dtype);
   const long P = (long)d->B * d->H * d->W;
   BwdWs w{};
   auto al = [](size_t v) { return (v + 255) / 256 * 256; };
@@ -889,6 +889,7 @@ extern "C" int dfm_convffn_fwd(int dtype, const DfmConvFFNDesc* d, const void* x
                                const float* bpos, const void* w2, const float* b2, const float* ls,
                                const float* rowscale, void* out, void* f, void* h, void* xn, float* mean,
                                float* rstd, void* gelu_out, void* gelu_grad, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);  // float32 is a known dtype without fused kernels: the argument error below
   DFM_CHECK_ARG(dfm_convffn_supported(dtype, d), "dfm_convffn_fwd: unsupported dtype %d / shape (C %d, hidden %d)",
                 dtype, d ? d->C : -1, d ? d->hidden : -1);
   DFM_CHECK_ARG(x && ln_w && ln_b && w1 && b1 && wpos && bpos && w2 && b2 && ls && out && f && h && mean && rstd,
@@ -903,12 +904,7 @@ extern "C" int dfm_convffn_fwd(int dtype, const DfmConvFFNDesc* d, const void* x
   a.out = out; a.f = f; a.h = h; a.xn = xn; a.mean = mean; a.rstd = rstd;
   a.gout = gelu_out; a.gdout = gelu_grad;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DFM_BF16) {
-    using T = bf16_t;
-    return FFN_C_SWITCH(d->C, ffn_fwd_launch, d, a, s);
-  }
-  using T = f16_t;
-  return FFN_C_SWITCH(d->C, ffn_fwd_launch, d, a, s);
+  DFM_DTYPE_SWITCH16(dtype, T, return FFN_C_SWITCH(d->C, ffn_fwd_launch, d, a, s));
 }
 
 extern "C" size_t dfm_convffn_bwd_workspace_size(int dtype, const DfmConvFFNDesc* d) {
@@ -923,6 +919,7 @@ extern "C" int dfm_convffn_bwd(int dtype, const DfmConvFFNDesc* d, const void* d
                                float* dln_w, float* dln_b, float* dw1, float* db1, float* dwpos, float* dbpos,
                                float* dw2, float* db2, float* dls, void* workspace, size_t workspace_bytes,
                                dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);  // float32: the argument error below, as in the forward
   DFM_CHECK_ARG(dfm_convffn_supported(dtype, d), "dfm_convffn_bwd: unsupported dtype %d / shape (C %d, hidden %d)",
                 dtype, d ? d->C : -1, d ? d->hidden : -1);
   DFM_CHECK_ARG(dout && x && h && xn && f && mean && rstd && ln_w && ln_b && w1 && wpos && bpos && w2 && ls && dx &&
@@ -960,13 +957,7 @@ extern "C" int dfm_convffn_bwd(int dtype, const DfmConvFFNDesc* d, const void* d
   // dhpre (+ dW2, db2) -> depthwise input / weight gradients -> fc1 weight gradient (+ db1)
   const BwdPlan p = dh_plan(d);
   a.dh = dhp;
-  if (dtype == DFM_BF16) {
-    using T = bf16_t;
-    rc = FFN_C_SWITCH(C, ffn_dh_launch, p, a, s);
-  } else {
-    using T = f16_t;
-    rc = FFN_C_SWITCH(C, ffn_dh_launch, p, a, s);
-  }
+  DFM_DTYPE_SWITCH16(dtype, T, rc = FFN_C_SWITCH(C, ffn_dh_launch, p, a, s));
   if (rc != DFM_OK) return rc;
   sums[ns++] = DfmPartialSum{pw2, dw2, nullptr, (long)C * R, 0, p.nstrip, 0, 0};
   sums[ns++] = DfmPartialSum{pb2, db2, nullptr, (long)C, 0, p.nstrip, 0, 0};

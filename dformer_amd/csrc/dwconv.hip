@@ -1492,29 +1492,19 @@ int dw_fwd(int B, int H, int W, int C, int k, const void* x, long ldx, const flo
 extern "C" int dfm_dwconv_fwd(int dtype, int B, int H, int W, int C, int k, const void* x, long ldx, const float* w,
                               const float* bias, int add_identity, void* y, long ldy, void* gout, long ldg,
                               dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(x && w && y && B > 0 && H > 0 && W > 0 && C > 0, "dfm_dwconv_fwd: bad argument");
-  if (dtype == DFM_BF16) return dw_fwd<bf16_t, false>(B, H, W, C, k, x, ldx, w, bias, add_identity, y, ldy, 0, gout, ldg, (hipStream_t)stream);
-  else if (dtype == DFM_F16) return dw_fwd<f16_t, false>(B, H, W, C, k, x, ldx, w, bias, add_identity, y, ldy, 0, gout, ldg, (hipStream_t)stream);
-  if (dtype == DFM_F32) return dw_fwd<float, false>(B, H, W, C, k, x, ldx, w, bias, add_identity, y, ldy, 0, gout, ldg, (hipStream_t)stream);
-  dfm_set_error("dfm_dwconv_fwd: bad dtype");
-  return DFM_ERR_DTYPE;
+  DFM_DTYPE_SWITCH(dtype, T, return dw_fwd<T, false>(B, H, W, C, k, x, ldx, w, bias, add_identity, y, ldy, 0, gout, ldg,
+                                                     (hipStream_t)stream));
 }
 
 extern "C" int dfm_dwconv_bwd_data(int dtype, int B, int H, int W, int C, int k, const void* dy, long lddy,
                                    const float* w, int add_identity, void* dx, long lddx, int accumulate,
                                    dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(dy && w && dx && B > 0 && H > 0 && W > 0 && C > 0, "dfm_dwconv_bwd_data: bad argument");
-  if (dtype == DFM_BF16)
-    return dw_fwd<bf16_t, true>(B, H, W, C, k, dy, lddy, w, nullptr, add_identity, dx, lddx, accumulate, nullptr, 0,
-                                (hipStream_t)stream);
-  else if (dtype == DFM_F16)
-    return dw_fwd<f16_t, true>(B, H, W, C, k, dy, lddy, w, nullptr, add_identity, dx, lddx, accumulate, nullptr, 0,
-                                (hipStream_t)stream);
-  if (dtype == DFM_F32)
-    return dw_fwd<float, true>(B, H, W, C, k, dy, lddy, w, nullptr, add_identity, dx, lddx, accumulate, nullptr, 0,
-                               (hipStream_t)stream);
-  dfm_set_error("dfm_dwconv_bwd_data: bad dtype");
-  return DFM_ERR_DTYPE;
+  DFM_DTYPE_SWITCH(dtype, T, return dw_fwd<T, true>(B, H, W, C, k, dy, lddy, w, nullptr, add_identity, dx, lddx,
+                                                    accumulate, nullptr, 0, (hipStream_t)stream));
 }
 
 extern "C" size_t dfm_dwconv_bwd_weight_workspace(int B, int H, int W, int C, int k) {
@@ -1532,6 +1522,7 @@ extern "C" int dfm_dwconv_bwd(int dtype, int B, int H, int W, int C, int k, cons
                               const void* dy, long lddy, const float* w, int add_identity, void* dx, long lddx,
                               int accumulate, float* dw, float* db, void* workspace, DfmPartialSum* defer,
                               dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   if (defer) *defer = DfmPartialSum{};
   DFM_CHECK_ARG(x && dy && w && dx && dw && workspace, "dfm_dwconv_bwd: null argument");
   DFM_CHECK_ARG(k == 3 || (k == 7 && !add_identity), "dfm_dwconv_bwd: k=%d%s unsupported", k,
@@ -1540,49 +1531,21 @@ extern "C" int dfm_dwconv_bwd(int dtype, int B, int H, int W, int C, int k, cons
   hipStream_t s = (hipStream_t)stream;
   float* part = (float*)workspace;
   long nsb;
-  if (k == 7) {  // one pass over dy for the input and the weight gradient (dw7_bwd_fused_kernel)
-    if (dtype == DFM_BF16) {
-      DFM_CHECK_ARG(dw_aligned<bf16_t>(C, x, ldx) && dw_aligned<bf16_t>(C, dy, lddy) && dw_aligned<bf16_t>(C, dx, lddx),
-                    "dfm_dwconv_bwd: alignment");
-      nsb = b7_launch<bf16_t>(B, H, W, C, x, ldx, dy, lddy, w, dx, lddx, accumulate, part, s);
-    } else if (dtype == DFM_F16) {
-      DFM_CHECK_ARG(dw_aligned<f16_t>(C, x, ldx) && dw_aligned<f16_t>(C, dy, lddy) && dw_aligned<f16_t>(C, dx, lddx),
-                    "dfm_dwconv_bwd: alignment");
-      nsb = b7_launch<f16_t>(B, H, W, C, x, ldx, dy, lddy, w, dx, lddx, accumulate, part, s);
-    } else if (dtype == DFM_F32) {
-      DFM_CHECK_ARG(dw_aligned<float>(C, x, ldx) && dw_aligned<float>(C, dy, lddy) && dw_aligned<float>(C, dx, lddx),
-                    "dfm_dwconv_bwd: alignment");
-      nsb = b7_launch<float>(B, H, W, C, x, ldx, dy, lddy, w, dx, lddx, accumulate, part, s);
-    } else {
-      dfm_set_error("dfm_dwconv_bwd: bad dtype");
-      return DFM_ERR_DTYPE;
-    }
-    DFM_LAUNCH_CHECK();
-    return second_stage(2, (int)nsb, (long)C * 50, part, dw, db, 50L, 0, defer, s);
-  }
-  if (dtype == DFM_BF16) {
-    DFM_CHECK_ARG(dw_aligned<bf16_t>(C, x, ldx) && dw_aligned<bf16_t>(C, dy, lddy) && dw_aligned<bf16_t>(C, dx, lddx),
+  DFM_DTYPE_SWITCH(dtype, T, {
+    DFM_CHECK_ARG(dw_aligned<T>(C, x, ldx) && dw_aligned<T>(C, dy, lddy) && dw_aligned<T>(C, dx, lddx),
                   "dfm_dwconv_bwd: alignment");
-    nsb = b3_launch<bf16_t>(B, H, W, C, x, ldx, dy, lddy, w, add_identity, dx, lddx, accumulate, part, s);
-  } else if (dtype == DFM_F16) {
-    DFM_CHECK_ARG(dw_aligned<f16_t>(C, x, ldx) && dw_aligned<f16_t>(C, dy, lddy) && dw_aligned<f16_t>(C, dx, lddx),
-                  "dfm_dwconv_bwd: alignment");
-    nsb = b3_launch<f16_t>(B, H, W, C, x, ldx, dy, lddy, w, add_identity, dx, lddx, accumulate, part, s);
-  } else if (dtype == DFM_F32) {
-    DFM_CHECK_ARG(dw_aligned<float>(C, x, ldx) && dw_aligned<float>(C, dy, lddy) && dw_aligned<float>(C, dx, lddx),
-                  "dfm_dwconv_bwd: alignment");
-    nsb = b3_launch<float>(B, H, W, C, x, ldx, dy, lddy, w, add_identity, dx, lddx, accumulate, part, s);
-  } else {
-    dfm_set_error("dfm_dwconv_bwd: bad dtype");
-    return DFM_ERR_DTYPE;
-  }
+    // k = 7: one pass over dy for the input and the weight gradient (dw7_bwd_fused_kernel)
+    nsb = k == 7 ? b7_launch<T>(B, H, W, C, x, ldx, dy, lddy, w, dx, lddx, accumulate, part, s)
+                 : b3_launch<T>(B, H, W, C, x, ldx, dy, lddy, w, add_identity, dx, lddx, accumulate, part, s);
+  });
   DFM_LAUNCH_CHECK();
-  return second_stage(2, (int)nsb, (long)C * 10, part, dw, db, 10L, 0, defer, s);
+  return second_stage(2, (int)nsb, (long)C * (k * k + 1), part, dw, db, (long)(k * k + 1), 0, defer, s);
 }
 
 extern "C" int dfm_dwconv_bwd_weight(int dtype, int B, int H, int W, int C, int k, const void* x, long ldx,
                                      const void* dy, long lddy, float* dw, float* db, void* workspace,
                                      DfmPartialSum* defer, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   if (defer) *defer = DfmPartialSum{};
   DFM_CHECK_ARG(x && dy && dw && workspace, "dfm_dwconv_bwd_weight: null argument");
   DFM_CHECK_ARG(k == 3 || k == 7, "dfm_dwconv_bwd_weight: k=%d unsupported", k);
@@ -1590,23 +1553,11 @@ extern "C" int dfm_dwconv_bwd_weight(int dtype, int B, int H, int W, int C, int 
   hipStream_t s = (hipStream_t)stream;
   float* part = (float*)workspace;
   long nsb;
-  if (dtype == DFM_BF16) {
-    DFM_CHECK_ARG(dw_aligned<bf16_t>(C, x, ldx) && dw_aligned<bf16_t>(C, dy, lddy), "dwconv wgrad: alignment");
-    nsb = k == 7 ? w7l_launch<bf16_t>(B, H, W, C, x, ldx, dy, lddy, part, s)
-                 : w3_launch<bf16_t>(B, H, W, C, x, ldx, dy, lddy, part, s);
-  }
-  else if (dtype == DFM_F16) {
-    DFM_CHECK_ARG(dw_aligned<f16_t>(C, x, ldx) && dw_aligned<f16_t>(C, dy, lddy), "dwconv wgrad: alignment");
-    nsb = k == 7 ? w7l_launch<f16_t>(B, H, W, C, x, ldx, dy, lddy, part, s)
-                 : w3_launch<f16_t>(B, H, W, C, x, ldx, dy, lddy, part, s);
-  } else if (dtype == DFM_F32) {
-    DFM_CHECK_ARG(dw_aligned<float>(C, x, ldx) && dw_aligned<float>(C, dy, lddy), "dwconv wgrad: alignment");
-    nsb = k == 7 ? w7l_launch<float>(B, H, W, C, x, ldx, dy, lddy, part, s)
-                 : w3_launch<float>(B, H, W, C, x, ldx, dy, lddy, part, s);
-  } else {
-    dfm_set_error("dfm_dwconv_bwd_weight: bad dtype");
-    return DFM_ERR_DTYPE;
-  }
+  DFM_DTYPE_SWITCH(dtype, T, {
+    DFM_CHECK_ARG(dw_aligned<T>(C, x, ldx) && dw_aligned<T>(C, dy, lddy), "dwconv wgrad: alignment");
+    nsb = k == 7 ? w7l_launch<T>(B, H, W, C, x, ldx, dy, lddy, part, s)
+                 : w3_launch<T>(B, H, W, C, x, ldx, dy, lddy, part, s);
+  });
   DFM_LAUNCH_CHECK();
   return second_stage(2, (int)nsb, (long)C * (k * k + 1), part, dw, db, (long)(k * k + 1), 0, defer, s);
 }

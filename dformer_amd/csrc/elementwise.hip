@@ -278,35 +278,16 @@ template <int OP>
 int ew2d(int dtype, long rows, int C, const void* a, long lda, const void* b, long ldb, const float* cs,
          const float* rs, long rps, float alpha, void* d, long ldd, int acc, hipStream_t s) {
   if (rows * C == 0) return DFM_OK;
-  if (C % 8 == 0 && ew_al<float>(a, lda) && ew_al<float>(b, ldb) && ew_al<float>(d, ldd) &&
-      (dtype == DFM_BF16 || dtype == DFM_F16 || dtype == DFM_F32)) {
-    const unsigned gv = ew_grid(rows * C / 8);
-    if (dtype == DFM_BF16)
-      DFM_LAUNCH((ew2d_vec_kernel<bf16_t, OP>), dim3(gv), dim3(256), 0, s, rows, C, (const bf16_t*)a, lda,
-                         (const bf16_t*)b, ldb, cs, rs, rps > 0 ? rps : 1, alpha, (bf16_t*)d, ldd, acc);
-    else if (dtype == DFM_F16)
-      DFM_LAUNCH((ew2d_vec_kernel<f16_t, OP>), dim3(gv), dim3(256), 0, s, rows, C, (const f16_t*)a, lda,
-                         (const f16_t*)b, ldb, cs, rs, rps > 0 ? rps : 1, alpha, (f16_t*)d, ldd, acc);
+  const bool vec = C % 8 == 0 && ew_al<float>(a, lda) && ew_al<float>(b, ldb) && ew_al<float>(d, ldd);
+  const unsigned g = ew_grid(vec ? rows * C / 8 : rows * C);
+  DFM_DTYPE_SWITCH(dtype, T, {
+    if (vec)
+      DFM_LAUNCH((ew2d_vec_kernel<T, OP>), dim3(g), dim3(256), 0, s, rows, C, (const T*)a, lda, (const T*)b, ldb, cs,
+                 rs, rps > 0 ? rps : 1, alpha, (T*)d, ldd, acc);
     else
-      DFM_LAUNCH((ew2d_vec_kernel<float, OP>), dim3(gv), dim3(256), 0, s, rows, C, (const float*)a, lda,
-                         (const float*)b, ldb, cs, rs, rps > 0 ? rps : 1, alpha, (float*)d, ldd, acc);
-    DFM_LAUNCH_CHECK();
-    return DFM_OK;
-  }
-  const unsigned g = ew_grid(rows * C);
-  if (dtype == DFM_BF16)
-    DFM_LAUNCH((ew2d_kernel<bf16_t, OP>), dim3(g), dim3(256), 0, s, rows, C, (const bf16_t*)a, lda,
-                       (const bf16_t*)b, ldb, cs, rs, rps > 0 ? rps : 1, alpha, (bf16_t*)d, ldd, acc);
-  else if (dtype == DFM_F16)
-    DFM_LAUNCH((ew2d_kernel<f16_t, OP>), dim3(g), dim3(256), 0, s, rows, C, (const f16_t*)a, lda,
-                       (const f16_t*)b, ldb, cs, rs, rps > 0 ? rps : 1, alpha, (f16_t*)d, ldd, acc);
-  else if (dtype == DFM_F32)
-    DFM_LAUNCH((ew2d_kernel<float, OP>), dim3(g), dim3(256), 0, s, rows, C, (const float*)a, lda,
-                       (const float*)b, ldb, cs, rs, rps > 0 ? rps : 1, alpha, (float*)d, ldd, acc);
-  else {
-    dfm_set_error("elementwise: bad dtype");
-    return DFM_ERR_DTYPE;
-  }
+      DFM_LAUNCH((ew2d_kernel<T, OP>), dim3(g), dim3(256), 0, s, rows, C, (const T*)a, lda, (const T*)b, ldb, cs, rs,
+                 rps > 0 ? rps : 1, alpha, (T*)d, ldd, acc);
+  });
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
@@ -600,17 +581,18 @@ extern "C" size_t dfm_bn_workspace(long rows, int C) { return dfm_colsum_workspa
 
 extern "C" int dfm_colsum(int dtype, long rows, int C, const void* x, long ldx, const void* mul, long ldmul,
                           const float* rowscale, long rps, float* out, int accumulate, void* ws, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(x && out && ws && C > 0, "dfm_colsum: bad argument");
   if (rows == 0) return DFM_OK;
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DFM_BF16) return colred<bf16_t, 0>(rows, C, x, ldx, mul, ldmul, nullptr, rowscale, rps, out, accumulate, ws, s);
-  else if (dtype == DFM_F16) return colred<f16_t, 0>(rows, C, x, ldx, mul, ldmul, nullptr, rowscale, rps, out, accumulate, ws, s);
-  if (dtype == DFM_F32) return colred<float, 0>(rows, C, x, ldx, mul, ldmul, nullptr, rowscale, rps, out, accumulate, ws, s);
-  dfm_set_error("dfm_colsum: bad dtype");
-  return DFM_ERR_DTYPE;
+  DFM_DTYPE_SWITCH(dtype, T,
+                   return colred<T, 0>(rows, C, x, ldx, mul, ldmul, nullptr, rowscale, rps, out, accumulate, ws, s));
 }
 
+// the instantiated (in, out) pairs, as an explicit table: bf16 <-> f16 has no kernel
 extern "C" int dfm_cast(int din, int dout, long n, const void* x, void* y, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(din);
+  DFM_CHECK_DTYPE(dout);
   hipStream_t s = (hipStream_t)stream;
   if (n == 0) return DFM_OK;
   const unsigned g = ew_grid(n);
@@ -622,7 +604,7 @@ extern "C" int dfm_cast(int din, int dout, long n, const void* x, void* y, dfm_s
   else if (din == DFM_F16 && dout == DFM_F32) DFM_LAUNCH((cast_kernel<f16_t, float>), dim3(g), dim3(256), 0, s, n, (const f16_t*)x, (float*)y);
   else if (din == DFM_F16 && dout == DFM_F16) DFM_LAUNCH((cast_kernel<f16_t, f16_t>), dim3(g), dim3(256), 0, s, n, (const f16_t*)x, (f16_t*)y);
   else {
-    dfm_set_error("dfm_cast: bad dtype");
+    dfm_set_error("dfm_cast: unsupported dtype %d -> %d", din, dout);
     return DFM_ERR_DTYPE;
   }
   DFM_LAUNCH_CHECK();
@@ -680,36 +662,29 @@ __global__ __launch_bounds__(256) void pack_slices_vec_kernel(PackSrc src, int n
 
 extern "C" int dfm_pack_slices(int dtype_out, int n, const void* const* srcs, const int* src_dtypes, long rows,
                                int cols, void* dst, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype_out);
   DFM_CHECK_ARG(n >= 1 && n <= PACK_MAX && srcs && src_dtypes && dst && rows >= 0 && cols > 0,
                 "dfm_pack_slices: 1 <= n <= %d sources, non-null pointers", PACK_MAX);
   PackSrc ps{};
+  for (int i = 0; i < n; ++i) DFM_CHECK_DTYPE(src_dtypes[i]);
   for (int i = 0; i < n; ++i) {
     DFM_CHECK_ARG(srcs[i] != nullptr, "dfm_pack_slices: null source %d", i);
-    DFM_CHECK_ARG(src_dtypes[i] == DFM_F32 || src_dtypes[i] == DFM_BF16 || src_dtypes[i] == DFM_F16,
-                  "dfm_pack_slices: bad source dtype %d", src_dtypes[i]);
     ps.p[i] = srcs[i];
     ps.dt[i] = src_dtypes[i];
   }
   if (rows == 0) return DFM_OK;
   hipStream_t s = (hipStream_t)stream;
-  bool vec = cols % 8 == 0 && (dtype_out == DFM_BF16 || dtype_out == DFM_F16) && (uintptr_t)dst % 16 == 0;
+  // the vector kernel exists for 16-bit outputs only; float32 output always takes the scalar one
+  bool vec = cols % 8 == 0 && dfm_dtype_size(dtype_out) == 2 && (uintptr_t)dst % 16 == 0;
   for (int i = 0; i < n; ++i) vec = vec && (uintptr_t)srcs[i] % 16 == 0;
   if (vec) {
     const unsigned gv = ew_grid(rows * (long)n * cols / 8);
-    if (dtype_out == DFM_BF16)
-      DFM_LAUNCH(pack_slices_vec_kernel<bf16_t>, dim3(gv), dim3(256), 0, s, ps, n, rows, cols, (bf16_t*)dst);
-    else
-      DFM_LAUNCH(pack_slices_vec_kernel<f16_t>, dim3(gv), dim3(256), 0, s, ps, n, rows, cols, (f16_t*)dst);
-    DFM_LAUNCH_CHECK();
-    return DFM_OK;
-  }
-  const unsigned g = ew_grid(rows * (long)n * cols);
-  if (dtype_out == DFM_BF16) DFM_LAUNCH(pack_slices_kernel<bf16_t>, dim3(g), dim3(256), 0, s, ps, n, rows, cols, (bf16_t*)dst);
-  else if (dtype_out == DFM_F16) DFM_LAUNCH(pack_slices_kernel<f16_t>, dim3(g), dim3(256), 0, s, ps, n, rows, cols, (f16_t*)dst);
-  else if (dtype_out == DFM_F32) DFM_LAUNCH(pack_slices_kernel<float>, dim3(g), dim3(256), 0, s, ps, n, rows, cols, (float*)dst);
-  else {
-    dfm_set_error("dfm_pack_slices: bad dtype %d", dtype_out);
-    return DFM_ERR_DTYPE;
+    DFM_DTYPE_SWITCH16(dtype_out, T,
+                       DFM_LAUNCH(pack_slices_vec_kernel<T>, dim3(gv), dim3(256), 0, s, ps, n, rows, cols, (T*)dst));
+  } else {
+    const unsigned g = ew_grid(rows * (long)n * cols);
+    DFM_DTYPE_SWITCH(dtype_out, T,
+                     DFM_LAUNCH(pack_slices_kernel<T>, dim3(g), dim3(256), 0, s, ps, n, rows, cols, (T*)dst));
   }
   DFM_LAUNCH_CHECK();
   return DFM_OK;
@@ -780,12 +755,14 @@ extern "C" int dfm_partial_sum_group(int n, const DfmPartialSum* sums, dfm_strea
 
 extern "C" int dfm_gelu_bwd(int dtype, long rows, int C, const void* dy, long lddy, const void* pre, long ldpre,
                             void* dx, long lddx, int accumulate, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(dy && pre && dx, "dfm_gelu_bwd: null argument");
   return ew2d<1>(dtype, rows, C, dy, lddy, pre, ldpre, nullptr, nullptr, 1, 1.f, dx, lddx, accumulate, (hipStream_t)stream);
 }
 
 extern "C" int dfm_relu_bwd(int dtype, long rows, int C, const void* dy, long lddy, const void* y, long ldy, void* dx,
                             long lddx, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(dy && y && dx, "dfm_relu_bwd: null argument");
   return ew2d<2>(dtype, rows, C, dy, lddy, y, ldy, nullptr, nullptr, 1, 1.f, dx, lddx, 0, (hipStream_t)stream);
 }
@@ -793,6 +770,7 @@ extern "C" int dfm_relu_bwd(int dtype, long rows, int C, const void* dy, long ld
 extern "C" int dfm_scale_mul(int dtype, long rows, int C, const void* src, long ldsrc, const void* mul, long ldmul,
                              const float* colscale, const float* rowscale, long rps, float alpha, void* dst,
                              long lddst, int accumulate, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(src && dst, "dfm_scale_mul: null argument");
   return ew2d<0>(dtype, rows, C, src, ldsrc, mul, ldmul, colscale, rowscale, rps, alpha, dst, lddst, accumulate,
                  (hipStream_t)stream);
@@ -817,15 +795,15 @@ __global__ __launch_bounds__(256) void group_scale_kernel(long rows, int C, cons
 
 extern "C" int dfm_group_scale(int dtype, long rows, int C, const void* x, long ldx, const float* scale,
                                long rows_per_group, void* y, long ldy, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(x && y && scale && rows_per_group > 0 && C > 0, "dfm_group_scale: bad argument");
-  DFM_CHECK_ARG(dtype == DFM_BF16 || dtype == DFM_F16 || dtype == DFM_F32, "dfm_group_scale: bad dtype %d", dtype);
   if (rows == 0) return DFM_OK;
   hipStream_t s = (hipStream_t)stream;
   const bool vec = C % 8 == 0 && ew_al<float>(x, ldx) && ew_al<float>(y, ldy);
   if (!vec || dtype == DFM_F32) {  // fp32 / unaligned: the elementwise path, one group at a time
     for (long r0 = 0; r0 < rows; r0 += rows_per_group) {
       const long n = std::min(rows_per_group, rows - r0);
-      const long eb = dtype == DFM_F32 ? 4 : 2;
+      const long eb = dfm_dtype_size(dtype);
       const int rc = ew2d<0>(dtype, n, C, (const char*)x + r0 * ldx * eb, ldx, nullptr, 0,
                              scale + (r0 / rows_per_group) * C, nullptr, 1, 1.f, (char*)y + r0 * ldy * eb, ldy, 0, s);
       if (rc) return rc;
@@ -833,18 +811,16 @@ extern "C" int dfm_group_scale(int dtype, long rows, int C, const void* x, long 
     return DFM_OK;
   }
   const unsigned g = ew_grid(rows * C / 8);
-  if (dtype == DFM_BF16)
-    DFM_LAUNCH(group_scale_kernel<bf16_t>, dim3(g), dim3(256), 0, s, rows, C, (const bf16_t*)x, ldx, scale,
-               rows_per_group, (bf16_t*)y, ldy);
-  else
-    DFM_LAUNCH(group_scale_kernel<f16_t>, dim3(g), dim3(256), 0, s, rows, C, (const f16_t*)x, ldx, scale,
-               rows_per_group, (f16_t*)y, ldy);
+  DFM_DTYPE_SWITCH16(dtype, T,
+                     DFM_LAUNCH(group_scale_kernel<T>, dim3(g), dim3(256), 0, s, rows, C, (const T*)x, ldx, scale,
+                                rows_per_group, (T*)y, ldy));
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
 
 extern "C" int dfm_dual_mul(int dtype, long rows, int C, const void* src, long ldsrc, const void* m1, long ld1,
                             const void* m2, long ld2, void* o1, long ldo1, void* o2, long ldo2, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(src && m1 && m2 && o1 && o2, "dfm_dual_mul: null argument");
   if (rows * C == 0) return DFM_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -856,27 +832,21 @@ extern "C" int dfm_dual_mul(int dtype, long rows, int C, const void* src, long l
     return ew2d<0>(dtype, rows, C, src, ldsrc, m2, ld2, nullptr, nullptr, 1, 1.f, o2, ldo2, 0, s);
   }
   const unsigned g = ew_grid(rows * C / 8);
-  return DFM_DTYPE_SWITCH(dtype, T, [&] {
-    DFM_LAUNCH(dual_mul_vec_kernel<T>, dim3(g), dim3(256), 0, s, rows, C, (const T*)src, ldsrc, (const T*)m1, ld1,
-               (const T*)m2, ld2, (T*)o1, ldo1, (T*)o2, ldo2);
-    DFM_LAUNCH_CHECK();
-    return DFM_OK;
-  }());
+  DFM_DTYPE_SWITCH(dtype, T,
+                   DFM_LAUNCH(dual_mul_vec_kernel<T>, dim3(g), dim3(256), 0, s, rows, C, (const T*)src, ldsrc,
+                              (const T*)m1, ld1, (const T*)m2, ld2, (T*)o1, ldo1, (T*)o2, ldo2));
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
 }
 
 extern "C" int dfm_bn_stats(int dtype, long rows, int C, const void* x, long ldx, float* stats, void* ws,
                             dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(x && stats && ws, "dfm_bn_stats: null argument");
   hipStream_t s = (hipStream_t)stream;
   DFM_CHECK_ARG(rows > 0, "dfm_bn_stats: no rows");
-  if (dtype == DFM_BF16)
-    return colred<bf16_t, 1>(rows, C, x, ldx, nullptr, 0, nullptr, nullptr, 1, stats, 0, ws, s, stats + 2 * C);
-  else if (dtype == DFM_F16)
-    return colred<f16_t, 1>(rows, C, x, ldx, nullptr, 0, nullptr, nullptr, 1, stats, 0, ws, s, stats + 2 * C);
-  if (dtype == DFM_F32)
-    return colred<float, 1>(rows, C, x, ldx, nullptr, 0, nullptr, nullptr, 1, stats, 0, ws, s, stats + 2 * C);
-  dfm_set_error("dfm_bn_stats: bad dtype");
-  return DFM_ERR_DTYPE;
+  DFM_DTYPE_SWITCH(dtype, T, return colred<T, 1>(rows, C, x, ldx, nullptr, 0, nullptr, nullptr, 1, stats, 0, ws, s,
+                                                 stats + 2 * C));
 }
 
 extern "C" int dfm_bn_finalize(int C, const float* stats, double count, float eps, float momentum, float* mean,
@@ -899,31 +869,18 @@ extern "C" int dfm_bn_merge(int shards, int C, const float* parts, const float* 
 extern "C" int dfm_bn_apply(int dtype, long rows, int C, const void* x, long ldx, const float* mean, const float* rstd,
                             const float* gamma, const float* beta, const void* res, long ldres, int act, void* y,
                             long ldy, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   hipStream_t s = (hipStream_t)stream;
-  if (C % 8 == 0 && ew_al<float>(x, ldx) && ew_al<float>(res, ldres) && ew_al<float>(y, ldy)) {
-    const unsigned gv = ew_grid(rows * C / 8);
-    if (dtype == DFM_BF16)
-      DFM_LAUNCH(bn_apply_vec_kernel<bf16_t>, dim3(gv), dim3(256), 0, s, rows, C, (const bf16_t*)x, ldx, mean,
-                         rstd, gamma, beta, (const bf16_t*)res, ldres, act, (bf16_t*)y, ldy);
-    else if (dtype == DFM_F16)
-      DFM_LAUNCH(bn_apply_vec_kernel<f16_t>, dim3(gv), dim3(256), 0, s, rows, C, (const f16_t*)x, ldx, mean,
-                         rstd, gamma, beta, (const f16_t*)res, ldres, act, (f16_t*)y, ldy);
+  const bool vec = C % 8 == 0 && ew_al<float>(x, ldx) && ew_al<float>(res, ldres) && ew_al<float>(y, ldy);
+  const unsigned g = ew_grid(vec ? rows * C / 8 : rows * C);
+  DFM_DTYPE_SWITCH(dtype, T, {
+    if (vec)
+      DFM_LAUNCH(bn_apply_vec_kernel<T>, dim3(g), dim3(256), 0, s, rows, C, (const T*)x, ldx, mean, rstd, gamma, beta,
+                 (const T*)res, ldres, act, (T*)y, ldy);
     else
-      DFM_LAUNCH(bn_apply_vec_kernel<float>, dim3(gv), dim3(256), 0, s, rows, C, (const float*)x, ldx, mean,
-                         rstd, gamma, beta, (const float*)res, ldres, act, (float*)y, ldy);
-    DFM_LAUNCH_CHECK();
-    return DFM_OK;
-  }
-  const unsigned g = ew_grid(rows * C);
-  if (dtype == DFM_BF16)
-    DFM_LAUNCH(bn_apply_kernel<bf16_t>, dim3(g), dim3(256), 0, s, rows, C, (const bf16_t*)x, ldx, mean, rstd,
-                       gamma, beta, (const bf16_t*)res, ldres, act, (bf16_t*)y, ldy);
-  else if (dtype == DFM_F16)
-    DFM_LAUNCH(bn_apply_kernel<f16_t>, dim3(g), dim3(256), 0, s, rows, C, (const f16_t*)x, ldx, mean, rstd,
-                       gamma, beta, (const f16_t*)res, ldres, act, (f16_t*)y, ldy);
-  else
-    DFM_LAUNCH(bn_apply_kernel<float>, dim3(g), dim3(256), 0, s, rows, C, (const float*)x, ldx, mean, rstd,
-                       gamma, beta, (const float*)res, ldres, act, (float*)y, ldy);
+      DFM_LAUNCH(bn_apply_kernel<T>, dim3(g), dim3(256), 0, s, rows, C, (const T*)x, ldx, mean, rstd, gamma, beta,
+                 (const T*)res, ldres, act, (T*)y, ldy);
+  });
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
@@ -931,9 +888,7 @@ extern "C" int dfm_bn_apply(int dtype, long rows, int C, const void* x, long ldx
 extern "C" int dfm_bn_bwd_stats(int dtype, long rows, int C, const void* x, long ldx, const void* dy, long lddy,
                                 const float* mean, const float* rstd, float* stats2, void* ws, dfm_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DFM_BF16) return colred<bf16_t, 2>(rows, C, x, ldx, dy, lddy, mean, rstd, 1, stats2, 0, ws, s);
-  else if (dtype == DFM_F16) return colred<f16_t, 2>(rows, C, x, ldx, dy, lddy, mean, rstd, 1, stats2, 0, ws, s);
-  return colred<float, 2>(rows, C, x, ldx, dy, lddy, mean, rstd, 1, stats2, 0, ws, s);
+  DFM_DTYPE_SWITCH(dtype, T, return colred<T, 2>(rows, C, x, ldx, dy, lddy, mean, rstd, 1, stats2, 0, ws, s));
 }
 
 extern "C" int dfm_bn_bwd_apply(int dtype, long rows, int C, const void* x, long ldx, const void* dy, long lddy,
@@ -941,43 +896,29 @@ extern "C" int dfm_bn_bwd_apply(int dtype, long rows, int C, const void* x, long
                                 double count, void* dx, long lddx, int accumulate, dfm_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   const float inv_n = (float)(1.0 / count);
-  if (C % 8 == 0 && ew_al<float>(x, ldx) && ew_al<float>(dy, lddy) && ew_al<float>(dx, lddx)) {
-    const unsigned gv = ew_grid(rows * C / 8);
-    if (dtype == DFM_BF16)
-      DFM_LAUNCH(bn_bwd_apply_vec_kernel<bf16_t>, dim3(gv), dim3(256), 0, s, rows, C, (const bf16_t*)x, ldx,
-                         (const bf16_t*)dy, lddy, mean, rstd, gamma, stats2, inv_n, (bf16_t*)dx, lddx, accumulate);
-    else if (dtype == DFM_F16)
-      DFM_LAUNCH(bn_bwd_apply_vec_kernel<f16_t>, dim3(gv), dim3(256), 0, s, rows, C, (const f16_t*)x, ldx,
-                         (const f16_t*)dy, lddy, mean, rstd, gamma, stats2, inv_n, (f16_t*)dx, lddx, accumulate);
+  const bool vec = C % 8 == 0 && ew_al<float>(x, ldx) && ew_al<float>(dy, lddy) && ew_al<float>(dx, lddx);
+  const unsigned g = ew_grid(vec ? rows * C / 8 : rows * C);
+  DFM_DTYPE_SWITCH(dtype, T, {
+    if (vec)
+      DFM_LAUNCH(bn_bwd_apply_vec_kernel<T>, dim3(g), dim3(256), 0, s, rows, C, (const T*)x, ldx, (const T*)dy, lddy,
+                 mean, rstd, gamma, stats2, inv_n, (T*)dx, lddx, accumulate);
     else
-      DFM_LAUNCH(bn_bwd_apply_vec_kernel<float>, dim3(gv), dim3(256), 0, s, rows, C, (const float*)x, ldx,
-                         (const float*)dy, lddy, mean, rstd, gamma, stats2, inv_n, (float*)dx, lddx, accumulate);
-    DFM_LAUNCH_CHECK();
-    return DFM_OK;
-  }
-  const unsigned g = ew_grid(rows * C);
-  if (dtype == DFM_BF16)
-    DFM_LAUNCH(bn_bwd_apply_kernel<bf16_t>, dim3(g), dim3(256), 0, s, rows, C, (const bf16_t*)x, ldx,
-                       (const bf16_t*)dy, lddy, mean, rstd, gamma, stats2, inv_n, (bf16_t*)dx, lddx, accumulate);
-  else if (dtype == DFM_F16)
-    DFM_LAUNCH(bn_bwd_apply_kernel<f16_t>, dim3(g), dim3(256), 0, s, rows, C, (const f16_t*)x, ldx,
-                       (const f16_t*)dy, lddy, mean, rstd, gamma, stats2, inv_n, (f16_t*)dx, lddx, accumulate);
-  else
-    DFM_LAUNCH(bn_bwd_apply_kernel<float>, dim3(g), dim3(256), 0, s, rows, C, (const float*)x, ldx,
-                       (const float*)dy, lddy, mean, rstd, gamma, stats2, inv_n, (float*)dx, lddx, accumulate);
+      DFM_LAUNCH(bn_bwd_apply_kernel<T>, dim3(g), dim3(256), 0, s, rows, C, (const T*)x, ldx, (const T*)dy, lddy,
+                 mean, rstd, gamma, stats2, inv_n, (T*)dx, lddx, accumulate);
+  });
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
 
+// The optional 16-bit shadow copy of a float32 kernel's result: copy_dtype must be 16-bit, except that callers
+// without a copy may pass DFM_F32 (either instantiation then computes the same float32 results).
+static int copy_code(const void* copy, int copy_dtype) { return !copy && copy_dtype == DFM_F32 ? DFM_BF16 : copy_dtype; }
+
 extern "C" int dfm_nmf_update(long n, const float* a, const float* num, const float* den, float eps, float* out,
                               void* out16, int copy_dtype, dfm_stream_t stream) {
-  DFM_CHECK_ARG(!out16 || copy_dtype == DFM_BF16 || copy_dtype == DFM_F16, "dfm_nmf_update: bad copy dtype");
-  if (copy_dtype == DFM_F16)
-    DFM_LAUNCH(nmf_update_kernel<f16_t>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, a, num, den, eps, out,
-               (f16_t*)out16);
-  else
-    DFM_LAUNCH(nmf_update_kernel<bf16_t>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, a, num, den, eps,
-               out, (bf16_t*)out16);
+  DFM_DTYPE_SWITCH16(copy_code(out16, copy_dtype), TC,
+                     DFM_LAUNCH(nmf_update_kernel<TC>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, a, num,
+                                den, eps, out, (TC*)out16));
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
@@ -985,13 +926,9 @@ extern "C" int dfm_nmf_update(long n, const float* a, const float* num, const fl
 extern "C" int dfm_nmf_update_bwd(long n, const float* g, const float* a, const float* num, const float* den,
                                   const float* out, float eps, float* ga, int acc, float* gnum, float* gden,
                                   void* gnum16, int copy_dtype, dfm_stream_t stream) {
-  DFM_CHECK_ARG(!gnum16 || copy_dtype == DFM_BF16 || copy_dtype == DFM_F16, "dfm_nmf_update_bwd: bad copy dtype");
-  if (copy_dtype == DFM_F16)
-    DFM_LAUNCH(nmf_update_bwd_kernel<f16_t>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, g, a, num, den,
-               out, eps, ga, acc, gnum, gden, (f16_t*)gnum16);
-  else
-    DFM_LAUNCH(nmf_update_bwd_kernel<bf16_t>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, g, a, num, den,
-               out, eps, ga, acc, gnum, gden, (bf16_t*)gnum16);
+  DFM_DTYPE_SWITCH16(copy_code(gnum16, copy_dtype), TC,
+                     DFM_LAUNCH(nmf_update_bwd_kernel<TC>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, g, a,
+                                num, den, out, eps, ga, acc, gnum, gden, (TC*)gnum16));
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
@@ -1141,18 +1078,17 @@ static bool nmf_mm_al(const void* p) { return p == nullptr || (uintptr_t)p % 16 
 
 extern "C" int dfm_nmf_update_mm(int batch, long rows, int R, const float* a, const float* num, const float* M,
                                  float eps, float* den, float* out, void* out16, int copy_dtype, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE16(copy_code(out16, copy_dtype));
   DFM_CHECK_ARG(R == NMF_R, "dfm_nmf_update_mm: R=%d unsupported (64 only)", R);
   DFM_CHECK_ARG(batch > 0 && rows >= 0 && a && num && M && den && out, "dfm_nmf_update_mm: bad argument");
-  DFM_CHECK_ARG(!out16 || copy_dtype == DFM_BF16 || copy_dtype == DFM_F16, "dfm_nmf_update_mm: bad copy dtype");
   DFM_CHECK_ARG(nmf_mm_al(a) && nmf_mm_al(num) && nmf_mm_al(M) && nmf_mm_al(den) && nmf_mm_al(out),
                 "dfm_nmf_update_mm: 16-byte aligned operands required");
   if (rows == 0) return DFM_OK;
   const dim3 grid(cdiv(rows, 64), batch);
   hipStream_t s = (hipStream_t)stream;
-  if (copy_dtype == DFM_F16)
-    DFM_LAUNCH(nmf_update_mm_kernel<f16_t>, grid, dim3(256), 0, s, rows, a, num, M, eps, den, out, (f16_t*)out16);
-  else
-    DFM_LAUNCH(nmf_update_mm_kernel<bf16_t>, grid, dim3(256), 0, s, rows, a, num, M, eps, den, out, (bf16_t*)out16);
+  DFM_DTYPE_SWITCH16(copy_code(out16, copy_dtype), TC,
+                     DFM_LAUNCH(nmf_update_mm_kernel<TC>, grid, dim3(256), 0, s, rows, a, num, M, eps, den, out,
+                                (TC*)out16));
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
@@ -1161,22 +1097,19 @@ extern "C" int dfm_nmf_update_bwd_mm(int batch, long rows, int R, const float* g
                                      const float* a, const float* num, const float* den, const float* out, float eps,
                                      const float* Mg, float* ga, int accumulate_ga, float* gnum, float* gden,
                                      void* gnum16, int copy_dtype, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE16(copy_code(gnum16, copy_dtype));
   DFM_CHECK_ARG(R == NMF_R, "dfm_nmf_update_bwd_mm: R=%d unsupported (64 only)", R);
   DFM_CHECK_ARG(batch > 0 && rows >= 0 && g && a && num && den && out && ga && gnum && gden && (!A2 || S),
                 "dfm_nmf_update_bwd_mm: bad argument");
-  DFM_CHECK_ARG(!gnum16 || copy_dtype == DFM_BF16 || copy_dtype == DFM_F16, "dfm_nmf_update_bwd_mm: bad copy dtype");
   DFM_CHECK_ARG(nmf_mm_al(g) && nmf_mm_al(A2) && nmf_mm_al(S) && nmf_mm_al(a) && nmf_mm_al(num) && nmf_mm_al(den) &&
                     nmf_mm_al(out) && nmf_mm_al(Mg) && nmf_mm_al(ga) && nmf_mm_al(gnum) && nmf_mm_al(gden),
                 "dfm_nmf_update_bwd_mm: 16-byte aligned operands required");
   if (rows == 0) return DFM_OK;
   const dim3 grid(cdiv(rows, 64), batch);
   hipStream_t s = (hipStream_t)stream;
-  if (copy_dtype == DFM_F16)
-    DFM_LAUNCH(nmf_update_bwd_mm_kernel<f16_t>, grid, dim3(256), 0, s, rows, g, A2, S, a, num, den, out, eps, Mg, ga,
-               accumulate_ga, gnum, gden, (f16_t*)gnum16);
-  else
-    DFM_LAUNCH(nmf_update_bwd_mm_kernel<bf16_t>, grid, dim3(256), 0, s, rows, g, A2, S, a, num, den, out, eps, Mg, ga,
-               accumulate_ga, gnum, gden, (bf16_t*)gnum16);
+  DFM_DTYPE_SWITCH16(copy_code(gnum16, copy_dtype), TC,
+                     DFM_LAUNCH(nmf_update_bwd_mm_kernel<TC>, grid, dim3(256), 0, s, rows, g, A2, S, a, num, den, out,
+                                eps, Mg, ga, accumulate_ga, gnum, gden, (TC*)gnum16));
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
@@ -1206,17 +1139,14 @@ extern "C" int dfm_softmax_rows_bwd(long rows, int R, const float* y, const floa
 extern "C" int dfm_adamw(long n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2,
                          float eps, float wd, int step, float gscale, void* copy, int copy_dtype,
                          dfm_stream_t stream) {
+  DFM_CHECK_DTYPE16(copy_code(copy, copy_dtype));
   DFM_CHECK_ARG(p && g && m && v && step >= 1, "dfm_adamw: bad argument");
-  DFM_CHECK_ARG(!copy || copy_dtype == DFM_BF16 || copy_dtype == DFM_F16, "dfm_adamw: bad copy dtype");
   if (n == 0) return DFM_OK;
   const float bc1 = 1.f - powf(beta1, (float)step);
   const float bc2 = 1.f - powf(beta2, (float)step);
-  if (copy_dtype == DFM_F16)
-    DFM_LAUNCH(adamw_kernel<f16_t>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v, lr, beta1,
-               beta2, eps, wd, bc1, sqrtf(bc2), gscale, (f16_t*)copy);
-  else
-    DFM_LAUNCH(adamw_kernel<bf16_t>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v, lr, beta1,
-               beta2, eps, wd, bc1, sqrtf(bc2), gscale, (bf16_t*)copy);
+  DFM_DTYPE_SWITCH16(copy_code(copy, copy_dtype), TC,
+                     DFM_LAUNCH(adamw_kernel<TC>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v, lr,
+                                beta1, beta2, eps, wd, bc1, sqrtf(bc2), gscale, (TC*)copy));
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
@@ -1224,15 +1154,12 @@ extern "C" int dfm_adamw(long n, float* p, const float* g, float* m, float* v, f
 extern "C" int dfm_adamw_dev(long n, float* p, const float* g, float* m, float* v, const float* hyper, float beta1,
                              float beta2, float eps, float wd, float gscale, void* copy, int copy_dtype,
                              dfm_stream_t stream) {
+  DFM_CHECK_DTYPE16(copy_code(copy, copy_dtype));
   DFM_CHECK_ARG(p && g && m && v && hyper, "dfm_adamw_dev: bad argument");
-  DFM_CHECK_ARG(!copy || copy_dtype == DFM_BF16 || copy_dtype == DFM_F16, "dfm_adamw_dev: bad copy dtype");
   if (n == 0) return DFM_OK;
-  if (copy_dtype == DFM_F16)
-    DFM_LAUNCH(adamw_dev_kernel<f16_t>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v, hyper,
-               beta1, beta2, eps, wd, gscale, (f16_t*)copy, nullptr, nullptr);
-  else
-    DFM_LAUNCH(adamw_dev_kernel<bf16_t>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v, hyper,
-               beta1, beta2, eps, wd, gscale, (bf16_t*)copy, nullptr, nullptr);
+  DFM_DTYPE_SWITCH16(copy_code(copy, copy_dtype), TC,
+                     DFM_LAUNCH(adamw_dev_kernel<TC>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v,
+                                hyper, beta1, beta2, eps, wd, gscale, (TC*)copy, nullptr, nullptr));
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
@@ -1240,15 +1167,12 @@ extern "C" int dfm_adamw_dev(long n, float* p, const float* g, float* m, float* 
 extern "C" int dfm_adamw_amp(long n, float* p, const float* g, float* m, float* v, const float* hyper,
                              const float* amp, const int* flag, float beta1, float beta2, float eps, float wd,
                              float gscale, void* copy, int copy_dtype, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE16(copy_code(copy, copy_dtype));
   DFM_CHECK_ARG(p && g && m && v && hyper && amp && flag, "dfm_adamw_amp: bad argument");
-  DFM_CHECK_ARG(!copy || copy_dtype == DFM_BF16 || copy_dtype == DFM_F16, "dfm_adamw_amp: bad copy dtype");
   if (n == 0) return DFM_OK;
-  if (copy_dtype == DFM_F16)
-    DFM_LAUNCH(adamw_dev_kernel<f16_t>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v, hyper,
-               beta1, beta2, eps, wd, gscale, (f16_t*)copy, amp, flag);
-  else
-    DFM_LAUNCH(adamw_dev_kernel<bf16_t>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v, hyper,
-               beta1, beta2, eps, wd, gscale, (bf16_t*)copy, amp, flag);
+  DFM_DTYPE_SWITCH16(copy_code(copy, copy_dtype), TC,
+                     DFM_LAUNCH(adamw_dev_kernel<TC>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v,
+                                hyper, beta1, beta2, eps, wd, gscale, (TC*)copy, amp, flag));
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
@@ -1317,6 +1241,7 @@ extern "C" size_t dfm_residual_bwd_workspace(long rows, int C) { return (size_t)
 extern "C" int dfm_residual_bwd(int dtype, long rows, int C, const void* dout, long lddout, const void* f, long ldf_,
                                 const float* colscale, const float* rowscale, long rps, void* df, long lddf,
                                 float* dscale, void* ws, DfmPartialSum* defer, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   if (defer) *defer = DfmPartialSum{};
   DFM_CHECK_ARG(dout && f && df && dscale && ws && C % 8 == 0 && C <= 2048, "dfm_residual_bwd: bad argument");
   DFM_CHECK_ARG(lddout % 8 == 0 && ldf_ % 8 == 0 && lddf % 8 == 0 && (uintptr_t)dout % 16 == 0 &&
@@ -1325,19 +1250,9 @@ extern "C" int dfm_residual_bwd(int dtype, long rows, int C, const void* dout, l
   if (rows == 0) return DFM_OK;
   hipStream_t s = (hipStream_t)stream;
   const int nblk = (int)min((long)RES_BLOCKS, max(1L, rows / 64));
-  if (dtype == DFM_BF16)
-    DFM_LAUNCH(residual_bwd_kernel<bf16_t>, dim3(nblk), dim3(256), 0, s, rows, C, (const bf16_t*)dout, lddout,
-                       (const bf16_t*)f, ldf_, colscale, rowscale, rps > 0 ? rps : 1, (bf16_t*)df, lddf, (float*)ws);
-  else if (dtype == DFM_F16)
-    DFM_LAUNCH(residual_bwd_kernel<f16_t>, dim3(nblk), dim3(256), 0, s, rows, C, (const f16_t*)dout, lddout,
-                       (const f16_t*)f, ldf_, colscale, rowscale, rps > 0 ? rps : 1, (f16_t*)df, lddf, (float*)ws);
-  else if (dtype == DFM_F32)
-    DFM_LAUNCH(residual_bwd_kernel<float>, dim3(nblk), dim3(256), 0, s, rows, C, (const float*)dout, lddout,
-                       (const float*)f, ldf_, colscale, rowscale, rps > 0 ? rps : 1, (float*)df, lddf, (float*)ws);
-  else {
-    dfm_set_error("dfm_residual_bwd: bad dtype");
-    return DFM_ERR_DTYPE;
-  }
+  DFM_DTYPE_SWITCH(dtype, T,
+                   DFM_LAUNCH(residual_bwd_kernel<T>, dim3(nblk), dim3(256), 0, s, rows, C, (const T*)dout, lddout,
+                              (const T*)f, ldf_, colscale, rowscale, rps > 0 ? rps : 1, (T*)df, lddf, (float*)ws));
   DFM_LAUNCH_CHECK();
   return second_stage(0, nblk, (long)C, (const float*)ws, dscale, nullptr, 0L, 0, defer, s);
 }

@@ -163,12 +163,15 @@ int msf_typed(int B, int h, int w, int ncls, const void* low, long ldl, int Hs, 
 extern "C" int dfm_resize_nchw(int dtype_in, int dtype_out, int B, int C, int Hi, int Wi, long sb, long sc, long sh,
                                long sw, const void* x, int Ho, int Wo, int align_corners, int flip, void* y,
                                dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype_in);
+  DFM_CHECK_DTYPE(dtype_out);
   DFM_CHECK_ARG(x && y && B > 0 && C > 0 && Hi > 0 && Wi > 0 && Ho > 0 && Wo > 0, "dfm_resize_nchw: bad argument");
   hipStream_t s = (hipStream_t)stream;
   const unsigned g = grid_for((long)B * C * Ho * Wo);
 #define DFM_RESIZE(TI, TO)                                                                                          \
   DFM_LAUNCH((resize_nchw_kernel<TI, TO>), dim3(g), dim3(kThreads), 0, s, B, C, Hi, Wi, sb, sc, sh, sw, Ho, Wo,      \
              align_corners, flip, (const TI*)x, (TO*)y)
+  // the instantiated (in, out) pairs, as an explicit table
   if (dtype_in == DFM_F32 && dtype_out == DFM_F32) DFM_RESIZE(float, float);
   else if (dtype_in == DFM_BF16 && dtype_out == DFM_F32) DFM_RESIZE(bf16_t, float);
   else if (dtype_in == DFM_F32 && dtype_out == DFM_BF16) DFM_RESIZE(float, bf16_t);
@@ -176,7 +179,7 @@ extern "C" int dfm_resize_nchw(int dtype_in, int dtype_out, int B, int C, int Hi
   else if (dtype_in == DFM_F16 && dtype_out == DFM_F32) DFM_RESIZE(f16_t, float);
   else if (dtype_in == DFM_F32 && dtype_out == DFM_F16) DFM_RESIZE(float, f16_t);
   else {
-    dfm_set_error("dfm_resize_nchw: unsupported dtypes %d -> %d", dtype_in, dtype_out);
+    dfm_set_error("dfm_resize_nchw: unsupported dtype %d -> %d", dtype_in, dtype_out);
     return DFM_ERR_DTYPE;
   }
 #undef DFM_RESIZE
@@ -186,15 +189,12 @@ extern "C" int dfm_resize_nchw(int dtype_in, int dtype_out, int B, int C, int Hi
 
 extern "C" int dfm_msf_accumulate(int dtype, int B, int h, int w, int ncls, const void* low, long ldl, int Hs, int Ws,
                                   int H, int W, int flip, float* acc, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(low && acc && B > 0 && h > 0 && w > 0 && Hs > 0 && Ws > 0 && H > 0 && W > 0 && ldl >= ncls,
                 "dfm_msf_accumulate: bad argument");
   DFM_CHECK_ARG(ncls > 0 && ncls <= kMaxCls, "dfm_msf_accumulate: ncls=%d outside [1, %d]", ncls, kMaxCls);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == DFM_BF16) return msf_typed<bf16_t>(B, h, w, ncls, low, ldl, Hs, Ws, H, W, flip, acc, s);
-  if (dtype == DFM_F16) return msf_typed<f16_t>(B, h, w, ncls, low, ldl, Hs, Ws, H, W, flip, acc, s);
-  if (dtype == DFM_F32) return msf_typed<float>(B, h, w, ncls, low, ldl, Hs, Ws, H, W, flip, acc, s);
-  dfm_set_error("dfm_msf_accumulate: unsupported dtype %d", dtype);
-  return DFM_ERR_DTYPE;
+  DFM_DTYPE_SWITCH(dtype, T, return msf_typed<T>(B, h, w, ncls, low, ldl, Hs, Ws, H, W, flip, acc, s));
 }
 
 extern "C" int dfm_seg_confusion(long npix, int ncls, const float* acc, const long long* label, int ignore,

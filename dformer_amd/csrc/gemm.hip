@@ -51,6 +51,7 @@ static int validate_desc(const DfmGemmDesc* d, const char* who, int q) {
 
 extern "C" int dfm_gemm(int dtype, const DfmGemmDesc* d, const void* A, const void* B, void* C, void* ws,
                         dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(d && A && B && C, "dfm_gemm: null argument");
   if (int st = validate_desc(d, "dfm_gemm", 0)) return st;
   if (d->M == 0 || d->N == 0) return DFM_OK;
@@ -58,11 +59,11 @@ extern "C" int dfm_gemm(int dtype, const DfmGemmDesc* d, const void* A, const vo
   DFM_CHECK_ARG(need == 0 || (ws != nullptr && (size_t)d->workspace_bytes >= need),
                 "dfm_gemm: workspace of %ld bytes, %zu needed", d->workspace_bytes, need);
   hipStream_t s = (hipStream_t)stream;
+  // named per-dtype instantiation units, not a template: a plain chain
   if (dtype == DFM_BF16) return dfm_gemm_bf16(d, A, B, C, ws, s);
   if (dtype == DFM_F16) return dfm_gemm_f16(d, A, B, C, ws, s);
   if (dtype == DFM_F32) return dfm_gemm_f32(d, A, B, C, ws, s);
-  dfm_set_error("dfm_gemm: unsupported dtype %d", dtype);
-  return DFM_ERR_DTYPE;
+  return dfm_dtype_error(__func__, dtype);
 }
 
 extern "C" size_t dfm_gemm_group_workspace_size(int n, const DfmGemmDesc* d) {
@@ -84,6 +85,7 @@ extern "C" size_t dfm_gemm_group_workspace_size(int n, const DfmGemmDesc* d) {
 
 extern "C" int dfm_gemm_group(int dtype, int n, const DfmGemmDesc* d, const void* const* A, const void* const* B,
                               void* const* C, void* ws, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(d && A && B && C && n >= 1 && n <= GMAX, "dfm_gemm_group: 1 <= n <= %d problems", GMAX);
   for (int q = 0; q < n; ++q) {
     DFM_CHECK_ARG(A[q] && B[q] && C[q], "dfm_gemm_group: null operand (problem %d)", q);
@@ -99,6 +101,5 @@ extern "C" int dfm_gemm_group(int dtype, int n, const DfmGemmDesc* d, const void
   if (dtype == DFM_BF16) return dfm_gemm_group_bf16(n, d, A, B, C, ws, s);
   if (dtype == DFM_F16) return dfm_gemm_group_f16(n, d, A, B, C, ws, s);
   if (dtype == DFM_F32) return dfm_gemm_group_f32(n, d, A, B, C, ws, s);
-  dfm_set_error("dfm_gemm_group: unsupported dtype %d", dtype);
-  return DFM_ERR_DTYPE;
+  return dfm_dtype_error(__func__, dtype);
 }

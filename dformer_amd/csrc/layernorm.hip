@@ -423,14 +423,12 @@ int ln_bwd(long rows, int C, const void* x, long ldx, const void* dy, long lddy,
 extern "C" int dfm_layernorm_fwd(int dtype, long rows, int C, const void* x, long ldx, const float* gamma,
                                  const float* beta, float eps, void* y, long ldy, float* mean, float* rstd,
                                  dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(C > 0 && C <= 64 * MAXE, "dfm_layernorm_fwd: C=%d unsupported (max %d)", C, 64 * MAXE);
   DFM_CHECK_ARG(x && y && gamma && beta && mean && rstd, "dfm_layernorm_fwd: null argument");
   if (rows == 0) return DFM_OK;
-  if (dtype == DFM_BF16) return ln_fwd<bf16_t>(rows, C, x, ldx, gamma, beta, eps, y, ldy, mean, rstd, (hipStream_t)stream);
-  else if (dtype == DFM_F16) return ln_fwd<f16_t>(rows, C, x, ldx, gamma, beta, eps, y, ldy, mean, rstd, (hipStream_t)stream);
-  if (dtype == DFM_F32) return ln_fwd<float>(rows, C, x, ldx, gamma, beta, eps, y, ldy, mean, rstd, (hipStream_t)stream);
-  dfm_set_error("dfm_layernorm_fwd: bad dtype");
-  return DFM_ERR_DTYPE;
+  DFM_DTYPE_SWITCH(dtype, T,
+                   return ln_fwd<T>(rows, C, x, ldx, gamma, beta, eps, y, ldy, mean, rstd, (hipStream_t)stream));
 }
 
 extern "C" size_t dfm_layernorm_bwd_workspace(long rows, int C) {
@@ -442,20 +440,12 @@ extern "C" int dfm_layernorm_bwd(int dtype, long rows, int C, const void* x, lon
                                  const float* gamma, const float* mean, const float* rstd, const void* dres,
                                  long lddres, void* dx, long lddx, int accumulate, float* dgamma, float* dbeta,
                                  void* workspace, DfmPartialSum* defer, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   if (defer) *defer = DfmPartialSum{};  // n = 0: nothing to sum unless the first stage runs
   DFM_CHECK_ARG(C > 0 && C <= 1024, "dfm_layernorm_bwd: C=%d unsupported", C);
   DFM_CHECK_ARG(x && dy && dx && gamma && mean && rstd && dgamma && dbeta && workspace,
                 "dfm_layernorm_bwd: null argument");
   if (rows == 0) return DFM_OK;
-  if (dtype == DFM_BF16)
-    return ln_bwd<bf16_t>(rows, C, x, ldx, dy, lddy, gamma, mean, rstd, dres, lddres, dx, lddx, accumulate, dgamma, dbeta,
-                          workspace, defer, (hipStream_t)stream);
-  else if (dtype == DFM_F16)
-    return ln_bwd<f16_t>(rows, C, x, ldx, dy, lddy, gamma, mean, rstd, dres, lddres, dx, lddx, accumulate, dgamma, dbeta,
-                          workspace, defer, (hipStream_t)stream);
-  if (dtype == DFM_F32)
-    return ln_bwd<float>(rows, C, x, ldx, dy, lddy, gamma, mean, rstd, dres, lddres, dx, lddx, accumulate, dgamma, dbeta,
-                         workspace, defer, (hipStream_t)stream);
-  dfm_set_error("dfm_layernorm_bwd: bad dtype");
-  return DFM_ERR_DTYPE;
+  DFM_DTYPE_SWITCH(dtype, T, return ln_bwd<T>(rows, C, x, ldx, dy, lddy, gamma, mean, rstd, dres, lddres, dx, lddx,
+                                              accumulate, dgamma, dbeta, workspace, defer, (hipStream_t)stream));
 }

@@ -605,19 +605,15 @@ extern "C" size_t dfm_seg_loss_bwd_workspace(int B, int h, int w, int ncls, int 
 extern "C" int dfm_seg_loss_fwd(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
                                 const long* label, int ignore, float* lse, float* loss_out, void* workspace,
                                 dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(logits && label && loss_out && workspace && ncls <= MAXC, "dfm_seg_loss_fwd: bad argument");
   hipStream_t s = (hipStream_t)stream;
   const long n = (long)B * H * W;
   const int nblk = (int)min((long)LOSS_BLOCKS, (n + 255) / 256);
-  if (dtype == DFM_BF16)
-    DFM_LAUNCH((ncls <= 40 ? seg_loss_fwd_kernel<bf16_t, 40> : seg_loss_fwd_kernel<bf16_t, MAXC>), dim3(nblk), dim3(256), 0, s, B, h, w, ncls, (const bf16_t*)logits, H, W,
-               label, ignore, lse, (float*)workspace);
-  else if (dtype == DFM_F16)
-    DFM_LAUNCH((ncls <= 40 ? seg_loss_fwd_kernel<f16_t, 40> : seg_loss_fwd_kernel<f16_t, MAXC>), dim3(nblk), dim3(256), 0, s, B, h, w, ncls, (const f16_t*)logits, H, W,
-               label, ignore, lse, (float*)workspace);
-  else
-    DFM_LAUNCH((ncls <= 40 ? seg_loss_fwd_kernel<float, 40> : seg_loss_fwd_kernel<float, MAXC>), dim3(nblk), dim3(256), 0, s, B, h, w, ncls, (const float*)logits, H, W,
-               label, ignore, lse, (float*)workspace);
+  DFM_DTYPE_SWITCH(dtype, T,
+                   DFM_LAUNCH((ncls <= 40 ? seg_loss_fwd_kernel<T, 40> : seg_loss_fwd_kernel<T, MAXC>), dim3(nblk),
+                              dim3(256), 0, s, B, h, w, ncls, (const T*)logits, H, W, label, ignore, lse,
+                              (float*)workspace));
   DFM_LAUNCH_CHECK();
   DFM_LAUNCH(seg_loss_sum_kernel, dim3(1), dim3(64), 0, s, nblk, (const float*)workspace, loss_out);
   DFM_LAUNCH_CHECK();
@@ -639,43 +635,29 @@ extern "C" size_t dfm_seg_loss_grad_partials_size(int B, int h, int w, int ncls,
 extern "C" int dfm_seg_loss_fwd_grad(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
                                      const long* label, int ignore, float* loss_out, float* grad_partials,
                                      dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   const int S = fused_scale(h, w, H, W);
   DFM_CHECK_ARG(logits && label && loss_out && grad_partials && ncls <= MAXC && S,
                 "dfm_seg_loss_fwd_grad: bad argument (needs ncls <= 64 and H = S h, W = S w, S in {4, 8})");
   hipStream_t s = (hipStream_t)stream;
   float* part = grad_partials;
   float* lpart = part + (long)B * (h + 1) * (w + 1) * 4 * ncls;
-  if (dtype == DFM_BF16)
-    return launch_fused_tiles<bf16_t>(S, B, h, w, ncls, logits, H, W, label, ignore, loss_out, part, lpart, s);
-  if (dtype == DFM_F16)
-    return launch_fused_tiles<f16_t>(S, B, h, w, ncls, logits, H, W, label, ignore, loss_out, part, lpart, s);
-  if (dtype == DFM_F32)
-    return launch_fused_tiles<float>(S, B, h, w, ncls, logits, H, W, label, ignore, loss_out, part, lpart, s);
-  dfm_set_error("dfm_seg_loss_fwd_grad: bad dtype %d", dtype);
-  return DFM_ERR_DTYPE;
+  DFM_DTYPE_SWITCH(dtype, T, return launch_fused_tiles<T>(S, B, h, w, ncls, logits, H, W, label, ignore, loss_out, part,
+                                                          lpart, s));
 }
 
 extern "C" int dfm_seg_loss_bwd_gather(int dtype_out, int B, int h, int w, int ncls, const float* grad_partials,
                                        const float* loss_out, const float* gscale, void* dlogits,
                                        dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype_out);
   DFM_CHECK_ARG(grad_partials && loss_out && dlogits && ncls > 0 && B > 0 && h > 0 && w > 0,
                 "dfm_seg_loss_bwd_gather: bad argument");
   hipStream_t s = (hipStream_t)stream;
   const long n = (long)B * h * w * ncls;
   const dim3 g((unsigned)std::min(8192L, (n + 255) / 256));
-  if (dtype_out == DFM_BF16)
-    DFM_LAUNCH(seg_loss_gather_scaled_kernel<bf16_t>, g, dim3(256), 0, s, B, h, w, ncls, grad_partials, loss_out,
-               gscale, (bf16_t*)dlogits);
-  else if (dtype_out == DFM_F16)
-    DFM_LAUNCH(seg_loss_gather_scaled_kernel<f16_t>, g, dim3(256), 0, s, B, h, w, ncls, grad_partials, loss_out,
-               gscale, (f16_t*)dlogits);
-  else if (dtype_out == DFM_F32)
-    DFM_LAUNCH(seg_loss_gather_scaled_kernel<float>, g, dim3(256), 0, s, B, h, w, ncls, grad_partials, loss_out,
-               gscale, (float*)dlogits);
-  else {
-    dfm_set_error("dfm_seg_loss_bwd_gather: bad dtype %d", dtype_out);
-    return DFM_ERR_DTYPE;
-  }
+  DFM_DTYPE_SWITCH(dtype_out, T,
+                   DFM_LAUNCH(seg_loss_gather_scaled_kernel<T>, g, dim3(256), 0, s, B, h, w, ncls, grad_partials,
+                              loss_out, gscale, (T*)dlogits));
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
@@ -684,20 +666,15 @@ extern "C" int dfm_seg_loss_bwd(int dtype, int B, int h, int w, int ncls, const 
                                 const long* label, int ignore, const float* lse, const float* loss_out,
                                 const float* gscale, float* dlogits, void* workspace, dfm_stream_t stream) {
   (void)lse;
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(logits && label && loss_out && dlogits && ncls <= MAXC && h <= H && w <= W,
                 "dfm_seg_loss_bwd: bad argument (needs ncls <= 64 and an upsampling resize)");
   hipStream_t s = (hipStream_t)stream;
   const long nl = (long)B * h * w * ncls;
   if (workspace && tile_scale(h, w, H, W)) {
     const int S = tile_scale(h, w, H, W);
-    if (dtype == DFM_BF16)
-      return launch_bwd_tiles<bf16_t>(S, B, h, w, ncls, logits, H, W, label, ignore, loss_out, gscale,
-                                      (float*)workspace, dlogits, s);
-    else if (dtype == DFM_F16)
-      return launch_bwd_tiles<f16_t>(S, B, h, w, ncls, logits, H, W, label, ignore, loss_out, gscale,
-                                      (float*)workspace, dlogits, s);
-    return launch_bwd_tiles<float>(S, B, h, w, ncls, logits, H, W, label, ignore, loss_out, gscale,
-                                   (float*)workspace, dlogits, s);
+    DFM_DTYPE_SWITCH(dtype, T, return launch_bwd_tiles<T>(S, B, h, w, ncls, logits, H, W, label, ignore, loss_out,
+                                                          gscale, (float*)workspace, dlogits, s));
   }
   // other scales: separable x-pass into the workspace, then the y-pass
   DFM_CHECK_ARG(workspace, "dfm_seg_loss_bwd: needs dfm_seg_loss_bwd_workspace bytes of workspace");
@@ -706,30 +683,15 @@ extern "C" int dfm_seg_loss_bwd(int dtype, int B, int h, int w, int ncls, const 
   float* rx = (float*)workspace;
   const unsigned nblk = (unsigned)((long)B * ((H + RY - 1) / RY) * ((w + PJ - 1) / PJ));
   const size_t lds = (size_t)XP_NT * (ncls + 1) * sizeof(float);
-  if (lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)seg_loss_bwd_xpass_kernel<bf16_t, 40>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)seg_loss_bwd_xpass_kernel<bf16_t, MAXC>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)seg_loss_bwd_xpass_kernel<f16_t, 40>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)seg_loss_bwd_xpass_kernel<f16_t, MAXC>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)seg_loss_bwd_xpass_kernel<float, 40>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)seg_loss_bwd_xpass_kernel<float, MAXC>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipGetLastError();  // a refused attribute must not read as this launch's error
-  }
-  if (dtype == DFM_BF16)
-    DFM_LAUNCH((ncls <= 40 ? seg_loss_bwd_xpass_kernel<bf16_t, 40> : seg_loss_bwd_xpass_kernel<bf16_t, MAXC>), dim3(nblk), dim3(XP_NT), lds, s, B, h, w, ncls,
-               (const bf16_t*)logits, H, W, label, ignore, loss_out, gscale, rx, RY, PJ);
-  else if (dtype == DFM_F16)
-    DFM_LAUNCH((ncls <= 40 ? seg_loss_bwd_xpass_kernel<f16_t, 40> : seg_loss_bwd_xpass_kernel<f16_t, MAXC>), dim3(nblk), dim3(XP_NT), lds, s, B, h, w, ncls,
-               (const f16_t*)logits, H, W, label, ignore, loss_out, gscale, rx, RY, PJ);
-  else
-    DFM_LAUNCH((ncls <= 40 ? seg_loss_bwd_xpass_kernel<float, 40> : seg_loss_bwd_xpass_kernel<float, MAXC>), dim3(nblk), dim3(XP_NT), lds, s, B, h, w, ncls,
-               (const float*)logits, H, W, label, ignore, loss_out, gscale, rx, RY, PJ);
+  DFM_DTYPE_SWITCH(dtype, T, {
+    const auto kern = ncls <= 40 ? seg_loss_bwd_xpass_kernel<T, 40> : seg_loss_bwd_xpass_kernel<T, MAXC>;
+    if (lds > 64 * 1024) {
+      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      (void)hipGetLastError();  // a refused attribute must not read as this launch's error
+    }
+    DFM_LAUNCH(kern, dim3(nblk), dim3(XP_NT), lds, s, B, h, w, ncls, (const T*)logits, H, W, label, ignore, loss_out,
+               gscale, rx, RY, PJ);
+  });
   DFM_LAUNCH_CHECK();
   DFM_LAUNCH(seg_loss_bwd_ypass_kernel, dim3((unsigned)std::min(8192L, (nl + 255) / 256)), dim3(256), 0, s, B, h,
              w, ncls, H, (const float*)rx, dlogits);

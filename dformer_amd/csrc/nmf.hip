@@ -137,9 +137,10 @@ extern "C" size_t dfm_nmf_fwd_workspace_size(int dtype, int batch, long N, long 
 extern "C" int dfm_nmf_fwd(int dtype, int batch, long N, long D, int R, int steps, float eps, const void* x,
                            const float* bases, void* y, void* saved, long saved_bytes, void* workspace,
                            long workspace_bytes, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(x && bases && y && workspace, "dfm_nmf_fwd: null argument");
   DFM_CHECK_ARG(nmf_shape_ok(dtype, batch, N, D, R, steps),
-                "dfm_nmf_fwd: unsupported dtype / shape (R=%d; the fused updates are rank 64)", R);
+                "dfm_nmf_fwd: unsupported shape (R=%d; the fused updates are rank 64)", R);
   const bool lp = dtype != DFM_F32, keep = saved != nullptr;
   const NmfDescs g(batch, N, D, R, steps, lp);
   const FwdSlots sl(batch, N, D, R, steps, lp, keep);
@@ -216,15 +217,16 @@ struct BwdSlots {
 extern "C" size_t dfm_nmf_bwd_workspace_size(int dtype, int batch, long N, long D, int R, int steps) {
   if (!nmf_shape_ok(dtype, batch, N, D, R, steps)) return 0;
   const NmfDescs g(batch, N, D, R, steps, dtype != DFM_F32);
-  return BwdSlots(batch, N, D, R, steps, dtype == DFM_F32 ? 4 : 2, g.ws).total;
+  return BwdSlots(batch, N, D, R, steps, dfm_dtype_size(dtype), g.ws).total;
 }
 
 extern "C" int dfm_nmf_bwd(int dtype, int batch, long N, long D, int R, int steps, float eps, const void* x,
                            const float* bases, const void* saved, long saved_bytes, const void* gy, void* gx,
                            void* workspace, long workspace_bytes, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
   DFM_CHECK_ARG(x && bases && saved && gy && gx && workspace, "dfm_nmf_bwd: null argument");
   DFM_CHECK_ARG(nmf_shape_ok(dtype, batch, N, D, R, steps),
-                "dfm_nmf_bwd: unsupported dtype / shape (R=%d; the fused updates are rank 64)", R);
+                "dfm_nmf_bwd: unsupported shape (R=%d; the fused updates are rank 64)", R);
   const bool lp = dtype != DFM_F32;
   const NmfDescs g(batch, N, D, R, steps, lp);
   const FwdSlots sl(batch, N, D, R, steps, lp, true);

@@ -7,7 +7,8 @@
  *     the library never allocates, never synchronises the host, and only enqueues on `stream`
  *     (a hipStream_t passed as void*; NULL = default stream);
  *   - return 0 on success, negative on bad arguments / unsupported dtype / launch failure;
- *     dfm_last_error() returns a thread-local message for the last failure;
+ *     dfm_last_error() returns a thread-local message for the last failure; an unknown dtype code is
+ *     rejected before anything else is looked at (DFM_ERR_DTYPE, "<entry point>: unsupported dtype <code>");
  *   - dtype selects the storage type of activations: DFM_F32, DFM_BF16 or DFM_F16 (IEEE half,
  *     the reference's torch.autocast(float16) path, utils/train.py:289). Statistics,
  *     accumulators, LayerNorm / BatchNorm affine params, biases, depthwise weights and

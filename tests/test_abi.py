@@ -138,3 +138,41 @@ def test_gemm_validation_rejects_bad_descriptors(bad):
     st = _lib.lib.dfm_gemm(_lib.BF16, desc, fake, fake, fake, fake if "split_k" in bad else None, None)
     assert st == -1, _lib.lib.dfm_last_error()
     assert _lib.lib.dfm_last_error().startswith(b"dfm_gemm: ")
+
+
+# Every int-returning entry point that takes a dtype code, with the position(s) of the code(s) among its
+# arguments (a literal list: other leading ints are batch sizes or counts, and copy_dtype sits near the end).
+DTYPE_ENTRY_POINTS = [
+    ("dfm_gemm", (0,)), ("dfm_gemm_group", (0,)), ("dfm_layernorm_fwd", (0,)), ("dfm_layernorm_bwd", (0,)),
+    ("dfm_residual_bwd", (0,)), ("dfm_dwconv_fwd", (0,)), ("dfm_dwconv_bwd_data", (0,)),
+    ("dfm_dwconv_bwd_weight", (0,)), ("dfm_dwconv_bwd", (0,)), ("dfm_convffn_fwd", (0,)), ("dfm_convffn_bwd", (0,)),
+    ("dfm_block_fwd", (0,)), ("dfm_block_bwd", (0,)), ("dfm_colsum", (0,)), ("dfm_cast", (0, 1)),
+    ("dfm_gelu_bwd", (0,)), ("dfm_relu_bwd", (0,)), ("dfm_scale_mul", (0,)), ("dfm_group_scale", (0,)),
+    ("dfm_dual_mul", (0,)), ("dfm_adaptive_pool7_fwd", (0,)), ("dfm_adaptive_pool7_bwd", (0,)),
+    ("dfm_bilinear_fwd", (0,)), ("dfm_bilinear_bwd", (0,)), ("dfm_pooled_attn_fwd", (0,)),
+    ("dfm_pooled_attn_bwd", (0,)), ("dfm_bn_stats", (0,)), ("dfm_bn_apply", (0,)), ("dfm_bn_bwd_stats", (0,)),
+    ("dfm_bn_bwd_apply", (0,)), ("dfm_conv3s2_im2col", (0, 1)), ("dfm_conv3s2_col2im", (0,)),
+    ("dfm_conv3s2_col2im_nchw", (0, 1)), ("dfm_conv3_weight_pack", (0,)), ("dfm_resize_nchw", (0, 1)),
+    ("dfm_msf_accumulate", (0,)), ("dfm_nmf_fwd", (0,)), ("dfm_nmf_bwd", (0,)), ("dfm_seg_loss_fwd", (0,)),
+    ("dfm_seg_loss_bwd", (0,)), ("dfm_seg_loss_fwd_grad", (0,)), ("dfm_seg_loss_bwd_gather", (0,)),
+    ("dfm_nmf_update", (7,)), ("dfm_nmf_update_bwd", (12,)), ("dfm_nmf_update_mm", (10,)),
+    ("dfm_nmf_update_bwd_mm", (17,)), ("dfm_adamw", (13,)), ("dfm_adamw_dev", (12,)), ("dfm_adamw_amp", (14,)),
+    ("dfm_pack_slices", (0,)),  # dtype_out only: its source codes sit in an array
+]
+
+
+@pytest.mark.parametrize("name,pos", [(n, p) for n, ps in DTYPE_ENTRY_POINTS for p in ps])
+def test_unknown_dtype_is_rejected_first(name, pos):
+    """An unknown dtype code wins over every other defect of the call (null pointers, empty shapes): the
+    status is DFM_ERR_DTYPE and the message is "<entry point>: unsupported dtype <code>". Nothing reaches a
+    kernel with these arguments even where a check is missing; the status is then another one."""
+    from dformer_amd import _lib
+    res, argtypes = _lib._SIGS[name]
+    assert res is ctypes.c_int and argtypes[pos] is ctypes.c_int, name
+    args = [0.0 if t in (ctypes.c_float, ctypes.c_double) else
+            0 if t in (ctypes.c_int, ctypes.c_long, ctypes.c_size_t) else None for t in argtypes]
+    args[pos] = 7
+    st = getattr(_lib.lib, name)(*args)
+    err = _lib.lib.dfm_last_error().decode()
+    assert st == -2, (name, st, err)
+    assert err.startswith(name + ": ") and "unsupported dtype 7" in err, err
