@@ -7,9 +7,12 @@
 //                       logits )  — the model's own upsampling (builder.py:203), the flip back
 //                       (val_mm.py:389) and the resize to the label size (val_mm.py:377-379,
 //                       390-392) composed per output pixel: 16 low-res taps, nothing materialised
+//   dfm_slide_msf_accumulate  the same with sliding-window inference (val_mm.py:257-322): the scaled
+//                       logits are the per-pixel average of the overlapping windows' upsampled
+//                       logits, gathered from every window's low-res logits
 //   dfm_seg_confusion   hist[t * ncls + argmax_c acc[p, c]] += 1 over pixels with t != ignore
 // Every output element is owned by one thread (no float atomics); the histogram uses integer
-// atomics, so all three are deterministic.
+// atomics, so all four are deterministic.
 #include "common.h"
 
 namespace {
@@ -109,6 +112,104 @@ __global__ __launch_bounds__(kThreads) void msf_accumulate_kernel(int B, int h, 
   }
 }
 
+// Sliding-window form (val_mm.py:257-322 slide_inference inside evaluate_msf): the scaled image is
+// covered by hg x wg windows of hc x wc pixels, window (gi, gj) starting at
+// (win_start(gi, hstride, hc, Hs), win_start(gj, wstride, wc, Ws)); low holds every window's low-res
+// logits, [hg*wg][B][h][w] rows. Per output pixel the 4 align_corners=True taps of the scaled grid are
+// each the average over the covering windows (ascending (gi, gj), summed then divided by the count,
+// like the reference's preds / count_mat) of that window's align_corners=False upsampling at the
+// tap: nothing of size [B, ncls, Hs, Ws] is materialised.
+DFM_INLINE int win_start(int g, int stride, int crop, int n) { return max(min(g * stride + crop, n) - crop, 0); }
+
+// kSlideLanes lanes share an output pixel: lane j owns classes j, j + kSlideLanes, ..., so a group's
+// loads of a low-res tap and its read-modify-write of the pixel's acc row are contiguous across lanes
+// (one thread per pixel strides ncls floats between lanes: measured 2.3-2.8x slower); the
+// softmax's max and sum go across the group's lanes.
+constexpr int kSlideLanes = 8;
+template <int G> DFM_INLINE float group_max(float v) {
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+template <typename T, int KC>
+__global__ __launch_bounds__(kThreads) void slide_msf_accumulate_kernel(
+    int B, int h, int w, int ncls, const T* __restrict__ low, long ldl, int hc, int wc, int hstride, int wstride,
+    int hg, int wg, int Hs, int Ws, int H, int W, int flip, int softmax, float* __restrict__ acc) {
+  constexpr int L = kSlideLanes, kPix = kThreads / L;
+  const int j = threadIdx.x % L;
+  const long n = (long)B * H * W;
+  // a group's lanes share p, so they leave the loop together and the cross-lane steps stay inside it
+  for (long p = blockIdx.x * (long)kPix + threadIdx.x / L; p < n; p += (long)gridDim.x * kPix) {
+    const int x = (int)(p % W);
+    const long t = p / W;
+    const int y = (int)(t % H);
+    const long b = t / H;
+    float z[KC];
+#pragma unroll
+    for (int k = 0; k < KC; ++k) z[k] = 0.f;
+    const Lin sy = lin_src(y, Hs, H, true), sx = lin_src(x, Ws, W, true);
+    for (int a = 0; a < 4; ++a) {
+      const int ys = (a >> 1) ? sy.i1 : sy.i0;
+      const int xs0 = (a & 1) ? sx.i1 : sx.i0;
+      const float wa = ((a >> 1) ? sy.l1 : sy.l0) * ((a & 1) ? sx.l1 : sx.l0);
+      const int xs = flip ? Ws - 1 - xs0 : xs0;
+      float l[KC];
+#pragma unroll
+      for (int k = 0; k < KC; ++k) l[k] = 0.f;
+      int count = 0;
+      for (int gi = 0; gi < hg; ++gi) {
+        const int y1 = win_start(gi, hstride, hc, Hs);
+        if (ys < y1 || ys >= y1 + hc) continue;
+        const Lin ly = lin_src(ys - y1, h, hc, false);
+        for (int gj = 0; gj < wg; ++gj) {
+          const int x1 = win_start(gj, wstride, wc, Ws);
+          if (xs < x1 || xs >= x1 + wc) continue;
+          const Lin lx = lin_src(xs - x1, w, wc, false);
+          const T* img = low + (((long)(gi * wg + gj) * B + b) * h) * w * ldl + j;
+          const T* p00 = img + ((long)ly.i0 * w + lx.i0) * ldl;
+          const T* p01 = img + ((long)ly.i0 * w + lx.i1) * ldl;
+          const T* p10 = img + ((long)ly.i1 * w + lx.i0) * ldl;
+          const T* p11 = img + ((long)ly.i1 * w + lx.i1) * ldl;
+#pragma unroll
+          for (int k = 0; k < KC; ++k)
+            if (j + k * L < ncls)
+              l[k] += ly.l0 * (lx.l0 * ldf(p00 + k * L) + lx.l1 * ldf(p01 + k * L)) +
+                      ly.l1 * (lx.l0 * ldf(p10 + k * L) + lx.l1 * ldf(p11 + k * L));
+          ++count;
+        }
+      }
+      const float cnt = (float)count;
+#pragma unroll
+      for (int k = 0; k < KC; ++k)
+        if (j + k * L < ncls) z[k] = fmaf(wa, l[k] / cnt, z[k]);
+    }
+    float* dst = acc + p * ncls + j;
+    if (!softmax) {
+#pragma unroll
+      for (int k = 0; k < KC; ++k)
+        if (j + k * L < ncls) dst[k * L] = z[k];
+      continue;
+    }
+    float mx = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < KC; ++k)
+      if (j + k * L < ncls) mx = fmaxf(mx, z[k]);
+    mx = group_max<L>(mx);
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < KC; ++k)
+      if (j + k * L < ncls) {
+        z[k] = expf(z[k] - mx);
+        s += z[k];
+      }
+    const float inv = 1.f / group_sum<L>(s);
+#pragma unroll
+    for (int k = 0; k < KC; ++k)
+      if (j + k * L < ncls) dst[k * L] += z[k] * inv;
+  }
+}
+
 __global__ __launch_bounds__(kThreads) void confusion_kernel(long npix, int ncls, const float* __restrict__ acc,
                                                              const long long* __restrict__ label, int ignore,
                                                              unsigned long long* __restrict__ hist) {
@@ -158,6 +259,27 @@ int msf_typed(int B, int h, int w, int ncls, const void* low, long ldl, int Hs, 
   return DFM_OK;
 }
 
+int slide_grids(int n, int crop, int stride) {  // val_mm.py:295-296
+  const int over = n - crop + stride - 1;
+  return (over > 0 ? over : 0) / stride + 1;
+}
+
+template <typename T>
+int slide_msf_typed(int B, int h, int w, int ncls, const void* low, long ldl, int hc, int wc, int hstride, int wstride,
+                    int Hs, int Ws, int H, int W, int flip, int softmax, float* acc, hipStream_t s) {
+  const int hg = slide_grids(Hs, hc, hstride), wg = slide_grids(Ws, wc, wstride);
+  const unsigned g = grid_for((long)B * H * W * kSlideLanes);
+#define DFM_SLIDE(NC)                                                                                        \
+  DFM_LAUNCH((slide_msf_accumulate_kernel<T, NC / kSlideLanes>), dim3(g), dim3(kThreads), 0, s, B, h, w, ncls, \
+             (const T*)low, ldl, hc, wc, hstride, wstride, hg, wg, Hs, Ws, H, W, flip, softmax, acc)
+  if (ncls <= 16) DFM_SLIDE(16);
+  else if (ncls <= 40) DFM_SLIDE(40);
+  else DFM_SLIDE(kMaxCls);
+#undef DFM_SLIDE
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
 }  // namespace
 
 extern "C" int dfm_resize_nchw(int dtype_in, int dtype_out, int B, int C, int Hi, int Wi, long sb, long sc, long sh,
@@ -195,6 +317,26 @@ extern "C" int dfm_msf_accumulate(int dtype, int B, int h, int w, int ncls, cons
   DFM_CHECK_ARG(ncls > 0 && ncls <= kMaxCls, "dfm_msf_accumulate: ncls=%d outside [1, %d]", ncls, kMaxCls);
   hipStream_t s = (hipStream_t)stream;
   DFM_DTYPE_SWITCH(dtype, T, return msf_typed<T>(B, h, w, ncls, low, ldl, Hs, Ws, H, W, flip, acc, s));
+}
+
+extern "C" int dfm_slide_msf_accumulate(int dtype, int B, int h, int w, int ncls, const void* low, long ldl, int hc,
+                                        int wc, int hstride, int wstride, int Hs, int Ws, int H, int W, int flip,
+                                        int softmax, float* acc, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  DFM_CHECK_ARG(low && acc, "dfm_slide_msf_accumulate: null pointer");
+  DFM_CHECK_ARG(ncls > 0 && ncls <= kMaxCls, "dfm_slide_msf_accumulate: ncls=%d outside [1, %d]", ncls, kMaxCls);
+  DFM_CHECK_ARG(B > 0 && h > 0 && w > 0 && hc > 0 && wc > 0 && H > 0 && W > 0 && ldl >= ncls,
+                "dfm_slide_msf_accumulate: bad argument");
+  DFM_CHECK_ARG(hstride > 0 && wstride > 0, "dfm_slide_msf_accumulate: stride %d x %d must be positive", hstride,
+                wstride);
+  // a stride beyond the crop would leave pixels that no window covers (the reference asserts on them)
+  DFM_CHECK_ARG(hstride <= hc && wstride <= wc, "dfm_slide_msf_accumulate: stride %d x %d exceeds the crop %d x %d",
+                hstride, wstride, hc, wc);
+  DFM_CHECK_ARG(Hs >= hc && Ws >= wc, "dfm_slide_msf_accumulate: scaled size %d x %d smaller than the crop %d x %d",
+                Hs, Ws, hc, wc);
+  hipStream_t s = (hipStream_t)stream;
+  DFM_DTYPE_SWITCH(dtype, T, return slide_msf_typed<T>(B, h, w, ncls, low, ldl, hc, wc, hstride, wstride, Hs, Ws, H, W,
+                                                       flip, softmax, acc, s));
 }
 
 extern "C" int dfm_seg_confusion(long npix, int ncls, const float* acc, const long long* label, int ignore,

@@ -517,7 +517,12 @@ class NMF2D(nn.Module):
 
     def _build_bases(self, B, D, device):
         if self.injected_bases is not None:
-            return self.injected_bases.to(device=device, dtype=torch.float32)
+            bases = self.injected_bases.to(device=device, dtype=torch.float32)
+            n0 = bases.shape[0]
+            if n0 != B * self.S and n0 > 0 and (B * self.S) % n0 == 0:
+                # a stack of k batches (sliding-window crops): image g*b0 + i gets the bases of image i
+                bases = bases.repeat((B * self.S) // n0, 1, 1)
+            return bases
         b = torch.rand(B * self.S, D, self.R, device=device, generator=self.generator)
         return b / b.norm(dim=1, keepdim=True).clamp_min(1e-12)  # F.normalize(dim=1)
 

@@ -6,8 +6,16 @@ ceil(s*H/32)*32 x ceil(s*W/32)*32 (bilinear, align_corners=True) [and flipped], 
 eval forward (ham head: 7 NMF steps), and one kernel folds the model's own logits upsampling
 (align_corners=False), the flip back, the resize to the label size (align_corners=True), the
 softmax and the accumulation over scales into a float32 [B*H*W, ncls] buffer; the confusion
-histogram is another kernel. Sliding-window inference (`slide_inference`) and prediction PNG
-export (`save_dir`) are not on the path and raise.
+histogram is another kernel.
+
+Sliding-window inference (val_mm.py:257-322 `slide_inference`, `evaluate_msf(..., sliding=True)`):
+the scaled image is cut into overlapping crops of `config.eval_crop_size` at a stride of
+int(`config.eval_stride_rate` * crop); the crops run through the model in stacks, their low-res
+logits land in one [G*B*h*w, ncls] buffer, and one kernel (`K.slide_msf_accumulate`) gathers, per
+label pixel, the covering windows' upsampled logits, averages them, and does the flip back, the
+resize to the label size, the softmax and the accumulation as above; no zero-padded full-size
+logits, sum or count map is materialised. Prediction PNG export (`save_dir`) is not on the path
+and raises.
 """
 import math
 
@@ -77,21 +85,79 @@ def msf_size(H, W, scale):
     return int(math.ceil(nh / 32)) * 32, int(math.ceil(nw / 32)) * 32
 
 
+def slide_windows(n, crop, stride):
+    """val_mm.py:295-306: the (start, end) of every sliding window along an axis of n pixels; the last
+    window is moved back so that it ends at n."""
+    out = []
+    for i in range(K.slide_grids(n, crop, stride)):
+        end = min(i * stride + crop, n)
+        out.append((max(end - crop, 0), end))
+    return out
+
+
+def slide_strides(crop_size, stride_rate):
+    """val_mm.py:288-291: (h_stride, w_stride) = int(rate * crop) per axis."""
+    strides = tuple(int(stride_rate * c) for c in crop_size)
+    if min(strides) <= 0:
+        raise ValueError(f"sliding-window stride int({stride_rate} * {tuple(crop_size)}) = {strides} must be positive")
+    if strides[0] > crop_size[0] or strides[1] > crop_size[1]:
+        raise ValueError(f"sliding-window stride {strides} exceeds the crop {tuple(crop_size)}: pixels between "
+                         f"windows would get no prediction")
+    return strides
+
+
+def _slide_low_rows(model, x, e, crop_size, strides, crop_batch):
+    """The low-res logits of every sliding window of the scaled (and flipped) inputs x, e:
+    ([G*B*h*w, ncls] rows, window-major, (B, h, w), (Hs, Ws) of the image the windows were cut from)."""
+    hc, wc = crop_size
+    if hc > x.shape[2] or wc > x.shape[3]:  # val_mm.py:280-286: both dimensions go to the crop size
+        x = K.resize_nchw(x, (hc, wc), True)
+        e = K.resize_nchw(e, (hc, wc), True)
+    B, _, Hs, Ws = x.shape
+    wins = [(y1, y2, x1, x2) for y1, y2 in slide_windows(Hs, hc, strides[0])
+            for x1, x2 in slide_windows(Ws, wc, strides[1])]
+    per = max(1, (crop_batch if crop_batch is not None else B) // B)  # whole windows per model call
+    buf, shape, off = None, None, 0
+    for i in range(0, len(wins), per):
+        chunk = wins[i:i + per]
+        cx = torch.cat([x[:, :, y1:y2, x1:x2] for y1, y2, x1, x2 in chunk], 0)
+        ce = torch.cat([e[:, :, y1:y2, x1:x2] for y1, y2, x1, x2 in chunk], 0)
+        rows, (b, h, w) = _nhwc_rows(model._low_logits(cx, ce))
+        if buf is None:
+            shape = (B, h, w)
+            buf = torch.empty(len(wins) * B * h * w, rows.shape[1], device=rows.device, dtype=rows.dtype)
+        buf[off:off + b * h * w].copy_(rows)
+        off += b * h * w
+    return buf, shape, (Hs, Ws)
+
+
 @torch.no_grad()
-def msf_scores(model, rgb, modal_x, num_classes, scales, flip, out_shape=None):
+def msf_scores(model, rgb, modal_x, num_classes, scales, flip, out_shape=None, crop_size=None, stride_rate=None,
+               crop_batch=None):
     """Summed softmax scores over scales (and flips) of one batch: float32 [B*H*W, ncls] rows
     (val_mm.py:355-392 for one batch; `scaled_logits` of the reference, channels last). Like the
     reference (val_mm.py:355-356) the scaled sizes and the score buffer follow the LABEL's
-    (B, H, W) = out_shape (default: the image's own size)."""
+    (B, H, W) = out_shape (default: the image's own size).
+
+    With crop_size = (hc, wc) every scale runs the reference's sliding-window inference: windows of
+    crop_size at a stride of int(stride_rate * crop), at most crop_batch images (default: one window
+    of the batch) per model call."""
     B, H, W = out_shape if out_shape is not None else (rgb.shape[0], rgb.shape[2], rgb.shape[3])
     if rgb.shape[0] != B or modal_x.shape[0] != B:
         raise ValueError(f"msf_scores: batch of the images {rgb.shape[0]} != labels {B}")
+    if crop_size is not None:
+        crop_size = tuple(int(c) for c in crop_size)
+        strides = slide_strides(crop_size, stride_rate)
     acc = torch.zeros(B * H * W, num_classes, device=rgb.device, dtype=torch.float32)
     for scale in scales:
         size = msf_size(H, W, scale)
         for f in ((False, True) if flip else (False,)):
             x = K.resize_nchw(rgb, size, True, flip=f)
             e = K.resize_nchw(modal_x, size, True, flip=f)
+            if crop_size is not None:
+                rows, (b, h, w), scaled = _slide_low_rows(model, x, e, crop_size, strides, crop_batch)
+                K.slide_msf_accumulate(rows, b, h, w, num_classes, crop_size, strides, scaled, (H, W), f, acc)
+                continue
             low = model._low_logits(x, e)
             rows, (b, h, w) = _nhwc_rows(low)
             K.msf_accumulate(rows, b, h, w, num_classes, size, (H, W), f, acc)
@@ -99,20 +165,42 @@ def msf_scores(model, rgb, modal_x, num_classes, scales, flip, out_shape=None):
 
 
 @torch.no_grad()
+def slide_inference(model, imgs, modal_xs, config, crop_batch=None):
+    """val_mm.py:257-322: the window-averaged logits of imgs, float32 [B, ncls, Hs', Ws'] (an NCHW
+    view of NHWC rows), (Hs', Ws') the image size after the reference's up-sizing to the crop."""
+    crop_size = tuple(int(c) for c in config.eval_crop_size)
+    strides = slide_strides(crop_size, config.eval_stride_rate)
+    ncls = config.num_classes
+    rows, (b, h, w), (Hs, Ws) = _slide_low_rows(model, imgs, modal_xs, crop_size, strides, crop_batch)
+    out = torch.empty(b * Hs * Ws, ncls, device=rows.device, dtype=torch.float32)
+    K.slide_msf_accumulate(rows, b, h, w, ncls, crop_size, strides, (Hs, Ws), (Hs, Ws), False, out, softmax=False)
+    return out.view(b, Hs, Ws, ncls).permute(0, 3, 1, 2)
+
+
+@torch.no_grad()
 def evaluate_msf(model, dataloader, config, device, scales, flip, engine=None, save_dir=None, sliding=False):
     """val_mm.py:325-472. dataloader yields dicts with 'rgb', 'modal_x', 'gt'. Returns the Metrics
-    (a list of every rank's Metrics when engine.distributed, like the reference)."""
-    if sliding:
-        raise NotImplementedError("evaluate_msf: slide_inference is outside the hot path (SURVEY.md §2)")
+    (a list of every rank's Metrics when engine.distributed, like the reference). sliding=True runs
+    every scale through sliding-window inference with config.eval_crop_size and
+    config.eval_stride_rate (and config.eval_crop_batch images per model call, when set)."""
     if save_dir is not None:
         raise NotImplementedError("evaluate_msf: prediction image export is outside the hot path (SURVEY.md §2)")
+    slide = {}
+    if sliding:
+        try:  # optional, and a dict-backed config raises KeyError for a missing name
+            crop_batch = config.eval_crop_batch
+        except (AttributeError, KeyError):
+            crop_batch = None
+        slide = dict(crop_size=tuple(config.eval_crop_size), stride_rate=config.eval_stride_rate,
+                     crop_batch=crop_batch)
+        slide_strides(slide["crop_size"], slide["stride_rate"])  # a bad rate fails before the first batch
     model.eval()
     metrics = Metrics(config.num_classes, config.background, device)
     for batch in dataloader:
         rgb = batch["rgb"].to(device)
         modal_x = batch["modal_x"].to(device)
         gt = batch["gt"].to(device)
-        acc = msf_scores(model, rgb, modal_x, config.num_classes, scales, flip, out_shape=tuple(gt.shape))
+        acc = msf_scores(model, rgb, modal_x, config.num_classes, scales, flip, out_shape=tuple(gt.shape), **slide)
         metrics.update_rows(acc, gt)
     if engine is not None and getattr(engine, "distributed", False):
         all_metrics = [None for _ in range(engine.world_size)]

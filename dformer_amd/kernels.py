@@ -878,6 +878,31 @@ def msf_accumulate(low_rows, B, h, w, ncls, scaled_hw, out_hw, flip, acc):
     return acc
 
 
+def slide_grids(n, crop, stride):
+    """val_mm.py:295-296: the number of sliding windows along an axis of n pixels."""
+    return max(n - crop + stride - 1, 0) // stride + 1
+
+
+def slide_msf_accumulate(low_rows, B, h, w, ncls, crop_hw, stride_hw, scaled_hw, out_hw, flip, acc, softmax=True):
+    """msf_accumulate over sliding windows: low_rows [G*B*h*w, ncls] holds the low-res logits of the
+    G = hg*wg windows (window-major) of crop_hw pixels that cover the scaled_hw image at stride_hw; the
+    scaled logits are their per-pixel average (val_mm.py:257-322). softmax=False stores the averaged
+    logits, resized to out_hw, into acc instead of adding their softmax."""
+    (hc, wc), (hs, ws), (Hs, Ws), (H, W) = crop_hw, stride_hw, scaled_hw, out_hw
+    if hs > 0 and ws > 0:  # the library rejects the rest; the buffers' sizes are only known here
+        G = slide_grids(Hs, hc, hs) * slide_grids(Ws, wc, ws)
+        if low_rows.dim() != 2 or low_rows.shape[0] < G * B * h * w or low_rows.shape[1] < ncls:
+            raise ValueError(f"slide_msf_accumulate: low rows {tuple(low_rows.shape)} do not hold {G} windows x "
+                             f"{B} x {h} x {w} x {ncls}")
+    if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != B * H * W * ncls:
+        raise ValueError(f"slide_msf_accumulate: acc {tuple(acc.shape)} {acc.dtype} is not contiguous float32 "
+                         f"[{B}*{H}*{W}, {ncls}]")
+    check(lib.dfm_slide_msf_accumulate(dtype_code(low_rows), B, h, w, ncls, ptr(low_rows), ld(low_rows), hc, wc, hs,
+                                       ws, Hs, Ws, H, W, int(flip), int(softmax), ptr(acc), stream()),
+          "dfm_slide_msf_accumulate")
+    return acc
+
+
 def seg_confusion(acc, label, ncls, ignore, hist):
     """hist [ncls*ncls] int64 += bincount(label*ncls + argmax(acc rows)) over label != ignore."""
     assert label.dtype == torch.int64 and hist.dtype == torch.int64 and acc.is_contiguous()

@@ -429,6 +429,20 @@ int dfm_msf_accumulate(int dtype, int B, int h, int w, int ncls, const void* low
                        int W, int flip, float* acc, dfm_stream_t stream);
 int dfm_seg_confusion(long npix, int ncls, const float* acc, const long long* label, int ignore,
                       unsigned long long* hist, dfm_stream_t stream);
+/* slide_msf_accumulate: msf_accumulate with the reference's sliding-window inference
+ *   (utils/val_mm.py:257-322). The (Hs, Ws) scaled image is covered by hg x wg windows of hc x wc pixels,
+ *   hg = max(Hs - hc + hstride - 1, 0) / hstride + 1, window gi starting at row
+ *   max(min(gi * hstride + hc, Hs) - hc, 0) (wg, columns likewise); low [hg*wg][B][h][w] x ldl holds every
+ *   window's low-res logits, window-major (g = gi * wg + gj). The scaled logit of a pixel is the sum, in
+ *   ascending (gi, gj) order, of the covering windows' align_corners=False upsamplings (h, w) -> (hc, wc)
+ *   at that pixel, divided by their count; flip reads column Ws-1-xs; the result is resized to (H, W) with
+ *   align_corners=True. softmax != 0: acc [B*H*W][ncls] += softmax over classes; softmax == 0: acc = the
+ *   averaged logits themselves (slide_inference, with (H, W) = (Hs, Ws)). Needs Hs >= hc, Ws >= wc,
+ *   0 < stride <= crop, ncls <= 64.
+ *   A new symbol only: no existing layout or signature changes, so dfm_abi_version() stays 13. */
+int dfm_slide_msf_accumulate(int dtype, int B, int h, int w, int ncls, const void* low, long ldl, int hc, int wc,
+                             int hstride, int wstride, int Hs, int Ws, int H, int W, int flip, int softmax,
+                             float* acc, dfm_stream_t stream);
 
 /* ---------------------------------------------------------------- NMF2D multiplicative update
  * ham_head.py:120-145:  out = a * num / (den + eps)  (float32), and its backward:
