@@ -180,6 +180,16 @@ _SIGS = {
 }
 
 
+ABI_VERSION = 13  # the dfm_abi_version() the structs and _SIGS above were written for
+
+
+def check_abi(lib):
+    got = lib.dfm_abi_version()
+    if got != ABI_VERSION:
+        raise ImportError(f"dformer_amd: {LIB_PATH} has ABI version {got}, these bindings expect {ABI_VERSION}; "
+                          f"rebuild it from this tree's csrc")
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"dformer_amd: native library missing at {LIB_PATH}; run "
@@ -189,6 +199,7 @@ def _load():
         f = getattr(lib, name)
         f.restype = res
         f.argtypes = args
+    check_abi(lib)
     return lib
 
 

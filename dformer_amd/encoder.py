@@ -16,7 +16,8 @@ import torch.nn.functional as F
 
 from . import kernels as K
 from .decoders import bn_batch_stats, bn_grad_stats, collectives_on
-from .functional import ATTN_PARAM_NAMES, AttentionFn, ConvFFNFn, gslot, invalidate_weights, register_side_stream
+from .functional import ATTN_PARAM_NAMES, AttentionFn, ConvFFNFn, gslot, invalidate_weights
+from .streams import fork, join, side_stream
 
 _EMPTY = {}
 
@@ -105,19 +106,6 @@ class Attention(nn.Module):
         return [vals[n] for n in ATTN_PARAM_NAMES]
 
 
-_SIDE = {}
-
-
-def _side_stream(dev):
-    """The RGB ConvFFN's stream: independent of the depth branch's ConvFFN (mlp_e2) within a Block, so
-    the two overlap (the stage-2/3 kernels alone leave most CUs idle)."""
-    s = _SIDE.get(dev)
-    if s is None:
-        s = _SIDE[dev] = torch.cuda.Stream(device=dev)
-        register_side_stream(s)
-    return s
-
-
 def _drop_path_scale(B, drop_prob, training, dev):
     """mmcv DropPath as a per-sample row scale: floor(keep + U[0,1)) / keep, or None."""
     if drop_prob == 0.0 or not training:
@@ -150,6 +138,8 @@ class Block(nn.Module):
         self._row_scales = None  # [4, B] DropPath scales drawn for the whole backbone by DFormer.forward
 
     def forward(self, x, x_e):
+        if not x.is_cuda:
+            raise RuntimeError("dformer_amd runs on the HIP library only (tensors must be on the GPU)")
         B, H, W, C = x.shape
         shape = (B, H, W)
         xr = x.reshape(B * H * W, C)
@@ -177,23 +167,13 @@ class Block(nn.Module):
         # latency-bound. (RGB on the side: 491.8 / 491.0 vs 488.2 / 487.8 images/s with the depth
         # ConvFFN there — the side stream's kernels get the smaller share of the CUs, and the join waited
         # 2.3 ms per step on the depth ConvFFN finishing after the RGB one, profiles/r06_queue_analysis.txt)
-        side = _side_stream(x.device) if x1.is_cuda else None
-        if side is not None:
-            main = torch.cuda.current_stream(x.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                K.TAG = st + ".mlp"
-                x2 = self.mlp.fused(x1, shape, rs[1], self.layer_scale_2)
-            x1.record_stream(side)
-            K.TAG = st + ".mlp_e2"
-            xe2 = self.mlp_e2.fused(xe1, shape, rs[3], self.layer_scale_2_e)
-            main.wait_stream(side)
-            x2.record_stream(main)
-        else:
+        side = side_stream(x.device, "ffn")
+        with fork(side, reads=(x1,)):
             K.TAG = st + ".mlp"
             x2 = self.mlp.fused(x1, shape, rs[1], self.layer_scale_2)
-            K.TAG = st + ".mlp_e2"
-            xe2 = self.mlp_e2.fused(xe1, shape, rs[3], self.layer_scale_2_e)
+        K.TAG = st + ".mlp_e2"
+        xe2 = self.mlp_e2.fused(xe1, shape, rs[3], self.layer_scale_2_e)
+        join(side, made=(x2,))
         return x2.view(B, H, W, C), xe2.view(B, H, W, C // 2)
 
 
@@ -413,14 +393,11 @@ class DFormer(nn.Module):
         # the two branches' stems / downsamples are independent: the depth one runs on the side
         # stream (its backward too) next to the RGB one on the step's stream (same box, alternated:
         # 506.2 / 509.8 vs 503.3 / 500.2 images/s; SyncBN keeps both on the step's stream)
-        side, main = _side_stream(x.device), torch.cuda.current_stream(x.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
+        side = side_stream(x.device, "ffn")
+        with fork(side, reads=(e,)):
             e2 = _run_downsample_native(seq_e, e, dt)
-        e.record_stream(side)
         x2 = _run_downsample_native(self.downsample_layers[i], x, dt)
-        main.wait_stream(side)
-        e2.record_stream(main)
+        join(side, made=(e2,))
         return x2, e2
 
     def forward(self, x, x_e):

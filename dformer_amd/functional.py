@@ -15,6 +15,7 @@ import weakref
 import torch
 
 from . import kernels as K
+from .streams import fork, join, side_stream
 
 # ---------------------------------------------------------------- compute-dtype weight cache
 _EPOCH = [0]
@@ -143,46 +144,10 @@ def gslot_rows(*ps):
 # next block's backward no longer waits for them. Measured (alternating runs): 492.2-495.9 vs
 # 499.1-501.9 images/s; the ConvFFNs' groups alone (490.6 / 492.2) or the attention's alone (486.5 /
 # 488.1) were slower. Groups under kernels.WG_STREAM_MIN_FLOPS stay on the current stream.
-_WG_STREAM = {}
-
-
-def _wg_stream(dev):
-    st = _WG_STREAM.get(dev)
-    if st is None:
-        st = _WG_STREAM[dev] = torch.cuda.Stream(device=dev)
-        register_side_stream(st)
-    return st
-
-
-def wgrad_group(dev=None):
+def wgrad_group(dev):
     """The weight-gradient queue of one Block backward (kernels.wgrad_group), flushed on the
-    weight-gradient stream for CUDA tensors."""
-    if dev is not None and dev.type == "cuda":
-        return K.wgrad_group(stream=_wg_stream(dev))
-    return K.wgrad_group()
-
-
-_SIDE_STREAMS = []
-
-
-def register_side_stream(s):
-    """Streams besides the step's own on which this package issues gradient-writing kernels (the
-    encoder's RGB ConvFFN stream, the attention-backward and weight-gradient streams)."""
-    if all(s is not t for t in _SIDE_STREAMS):
-        _SIDE_STREAMS.append(s)
-
-
-def join_streams(main=None):
-    """The current stream waits for everything issued so far on `main` (the stream the step's
-    backward was started from) and on every side stream of this package, so a collective enqueued
-    next sees every gradient slot complete whichever stream autograd ran its last hook on."""
-    streams = ([main] if main is not None else []) + _SIDE_STREAMS
-    if not streams:  # CPU tensors / nothing issued off the current stream
-        return
-    cur = torch.cuda.current_stream()
-    for s in streams:
-        if s is not None and s.device == cur.device and s != cur:
-            cur.wait_stream(s)
+    weight-gradient stream."""
+    return K.wgrad_group(stream=side_stream(dev, "wgrad"))
 
 
 def _cat1(*vs):
@@ -305,15 +270,6 @@ class ConvFFNFn(torch.autograd.Function):
 # branch on a side stream measured 381.6 vs 383.4 images/s and was dropped: it is short and the
 # fork / join costs what the overlap gains; a second backward stream for the pooled-attention
 # branch gained nothing either.)
-_ATTN_BWD_SIDE = {}
-
-
-def _attn_bwd_side(dev):
-    st = _ATTN_BWD_SIDE.get(dev)
-    if st is None:
-        st = _ATTN_BWD_SIDE[dev] = torch.cuda.Stream(device=dev)
-        register_side_stream(st)
-    return st
 
 
 class AttentionFn(torch.autograd.Function):
@@ -395,8 +351,7 @@ class AttentionFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dx1, dxe1):
         K.TAG = ctx.tag + ".bwd"
-        g0 = dx1 if dx1 is not None else dxe1
-        with wgrad_group(g0.device if g0 is not None else None):  # the Block attention's weight gradients
+        with wgrad_group((dx1 if dx1 is not None else dxe1).device):  # the Block attention's weight gradients
             return AttentionFn._backward(ctx, dx1, dxe1)                 # as grouped launches at the end
 
     @staticmethod
@@ -451,30 +406,14 @@ class AttentionFn(torch.autograd.Function):
             calls.append(lambda c: K.linear_dgrad(dpc, Wc[:, C:C + Ch], out=dfa, collect=c))
         # (measured on the step against df + two dual_mul passes: 478.3 / 480.8 vs 475.0 / 476.7 images/s)
         K.gemm_many(calls)
-        side = _attn_bwd_side(dev) if x.is_cuda else None
-        main = torch.cuda.current_stream(dev) if side is not None else None
-
-        def depth_branch():  # cxe = cx * xe',  xe' = e_back(DW7(e_fore(LN_e xe)))
-            if drop_depth and dxe1 is not None:  # the Block's x_e output is xe' itself
-                K.scale_mul(dxe1.contiguous(), out=dxep, accumulate=True)
-            ow, ob = gslot2(web), gslot(beb)
-            grads["web"], grads["beb"] = K.linear_wgrad(dxep, e2, out=ow, bias_grad=True, bias_out=ob)
-            de2 = K.linear_dgrad(dxep, wcast(dt, web))
-            ow, ob = gslot(wec), gslot(bec)
-            # (the one-pass 7x7 backward, dfm_dwconv_bwd k = 7, is 4-15 % faster alone but measured slower on the
-            # step: 477.0 / 477.4 vs 479.3 / 478.4 images/s; its 65 KB of LDS per block keeps the two streams'
-            # 7x7 backwards from sharing a CU)
-            grads["wec"], grads["bec"] = K.dwconv_bwd_weight(e1, de2, shape, 7, dw=ow, db=ob)
-            de1 = K.dwconv_bwd_data(de2, shape, wec, 7)
-            ow, ob = gslot2(wef), gslot(bef)
-            grads["wef"], grads["bef"] = K.linear_wgrad(de1, xen, out=ow, bias_grad=True, bias_out=ob)
-            return K.linear_dgrad(de1, wcast(dt, wef)), (dxep, de2, de1)
-
-        def rgb_part():  # the pooled attention, q * a and the 7x7 modulation branch
+        # The RGB part runs on the side stream and the depth branch on the step's stream: the side stream's
+        # kernels get the smaller share of the CUs, and with the depth branch there the join waited ~2 ms per
+        # step for it (profiles/r06_queue_analysis.txt); swapped: 495.7 / 495.1 vs 491.3 / 492.6 images/s
+        side = side_stream(dev, "attn_bwd")
+        with fork(side):  # the pooled attention, q * a and the 7x7 modulation branch
             dg = torch.empty(P, C, device=dev, dtype=dt)
-            dxn = dpooled = dkv = None
-
-            def pooled_branch():  # softmax(q_pool k^T) v over the pooled queries, DFormer.py:119-131
+            dxn = dpooled = dkv = do = dm = None
+            if window:  # softmax(q_pool k^T) v over the pooled queries, DFormer.py:119-131
                 kv, pooled, m, o, lse = saved_attn
                 dh = C // heads // 2
                 do = K.bilinear_bwd(dfa, (7, 7), (H, W), B)
@@ -488,11 +427,6 @@ class AttentionFn(torch.autograd.Function):
                 dxn = K.pool7_bwd(dpooled[:, :C], shape)
                 ow, ob = gslot2(wkv), gslot(bkv)
                 grads["wkv"], grads["bkv"] = K.linear_wgrad(dkv, g, out=ow, bias_grad=True, bias_out=ob)
-                return dxn, dpooled, dkv, (do, dm)
-
-            tmp = ()
-            if window:
-                dxn, dpooled, dkv, tmp = pooled_branch()
             # q * a (dq, da came out of the projection's input-gradient epilogue)
             ow, ob = gslot2(wa), gslot(ba)
             grads["wa"], grads["ba"] = K.linear_wgrad(da, apre, out=ow, bias_grad=True, bias_out=ob)
@@ -506,25 +440,25 @@ class AttentionFn(torch.autograd.Function):
             grads["wconv"], grads["bconv"] = K.dwconv_bwd_weight(g, dapre, shape, 7, dw=ow, db=ob)
             K.dwconv_bwd_data(dapre, shape, wconv, 7, dx=dg, accumulate=bool(window))
             K.scale_mul(dg, mul=lpre, out=dl)  # lpre holds GELU'(l pre-activation)
-            made = tuple(t for t in (dg, dapre, dkv, dpooled, dxn) + tuple(tmp) if t is not None)
-            return dxn, (dpooled[:, C:] if dpooled is not None else None), made
-
-        # The RGB part runs on the side stream and the depth branch on the step's stream: the side stream's
-        # kernels get the smaller share of the CUs, and with the depth branch there the join waited ~2 ms per
-        # step for it (profiles/r06_queue_analysis.txt); swapped: 495.7 / 495.1 vs 491.3 / 492.6 images/s
-        if side is not None:
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                dxn, dpooled_e, made = rgb_part()
-            dxen, _ = depth_branch()
-            main.wait_stream(side)
-            for t in made:  # side allocations read here or by the block's queued weight gradients
-                t.record_stream(main)
-        else:
-            dxen, _ = depth_branch()
-            dxn, dpooled_e, _ = rgb_part()
-        if dpooled_e is not None:
-            K.pool7_bwd(dpooled_e, shape, dx=dxen, accumulate=True)
+        # the depth branch: cxe = cx * xe',  xe' = e_back(DW7(e_fore(LN_e xe)))
+        if drop_depth and dxe1 is not None:  # the Block's x_e output is xe' itself
+            K.scale_mul(dxe1.contiguous(), out=dxep, accumulate=True)
+        ow, ob = gslot2(web), gslot(beb)
+        grads["web"], grads["beb"] = K.linear_wgrad(dxep, e2, out=ow, bias_grad=True, bias_out=ob)
+        de2 = K.linear_dgrad(dxep, wcast(dt, web))
+        ow, ob = gslot(wec), gslot(bec)
+        # (the one-pass 7x7 backward, dfm_dwconv_bwd k = 7, is 4-15 % faster alone but measured slower on the
+        # step: 477.0 / 477.4 vs 479.3 / 478.4 images/s; its 65 KB of LDS per block keeps the two streams'
+        # 7x7 backwards from sharing a CU)
+        grads["wec"], grads["bec"] = K.dwconv_bwd_weight(e1, de2, shape, 7, dw=ow, db=ob)
+        de1 = K.dwconv_bwd_data(de2, shape, wec, 7)
+        ow, ob = gslot2(wef), gslot(bef)
+        grads["wef"], grads["bef"] = K.linear_wgrad(de1, xen, out=ow, bias_grad=True, bias_out=ob)
+        dxen = K.linear_dgrad(de1, wcast(dt, wef))
+        # side allocations read from here on, or by the block's queued weight gradients
+        join(side, made=(dg, dapre, dkv, dpooled, dxn, do, dm))
+        if dpooled is not None:
+            K.pool7_bwd(dpooled[:, C:], shape, dx=dxen, accumulate=True)
         # q | q_cut | l
         dWqcl, dbqcl = K.linear_wgrad(dqcl, xn, bias_grad=True, out=gslot_rows(wq, wqc, wl),
                                       bias_out=gslot_rows(bq, bqc, bl))

@@ -5,10 +5,11 @@ All tensors are CUDA (HIP) tensors; 2-D operands are [rows, cols] views whose la
 Activations are float32 or bfloat16; statistics / params / param-grads are float32.
 """
 import ctypes
+from typing import NamedTuple
 
 import torch
 
-from . import _lib
+from . import _lib, streams
 from ._lib import check, dtype_code, lib, ptr, stream
 
 _ws_cache = {}
@@ -138,21 +139,11 @@ class wgrad_group:
             # (~2.5 GFLOP groups) 628.1 / 625.0 vs 639.9 / 639.0 images/s with none; from 8 GFLOP up: Tiny
             # 642.4 / 639.8 vs 639.5 / 638.7, DFormer-B flat (its ~5 GFLOP depth-branch ConvFFN groups stay);
             # from 4 GFLOP up: Tiny 651.2 / 649.5 vs 640.4 / 639.2, DFormer-B 496.9 / 504.7 vs 496.4 / 495.0
-            if self.stream is None or sum(it[5] for it in pending) < WG_STREAM_MIN_FLOPS:
-                if pending:
-                    flush_wgrad(pending)
-                if reds:
-                    flush_reductions(reds)
-            else:
-                self.stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(self.stream):
-                    for item in pending:  # operands written on the current stream, read on this one
-                        item[2].record_stream(self.stream)
-                        item[3].record_stream(self.stream)
-                    if pending:
-                        flush_wgrad(pending)
-                    if reds:
-                        flush_reductions(reds)
+            if self.stream is None or sum(it.flops for it in pending) < WG_STREAM_MIN_FLOPS:
+                _flush(pending, reds)
+            else:  # operands written on the current stream, read on this one
+                with streams.fork(self.stream, reads=[t for it in pending for t in (it.a, it.b)]):
+                    _flush(pending, reds)
         return False
 
 
@@ -179,27 +170,63 @@ def flush_reductions(reds):
         _acct(0, 0)
 
 
+class _GemmItem(NamedTuple):
+    """One GEMM ready to launch: from gemm_many's `collect=` or a wgrad_group's queue. `colsum` and `bias`
+    are only held so the tensors `desc` points at stay referenced until the launch."""
+    desc: _lib.GemmDesc
+    dtype: int
+    a: torch.Tensor
+    b: torch.Tensor
+    out: torch.Tensor
+    flops: float
+    nbytes: int
+    peak: str
+    colsum: object = None
+    bias: object = None
+
+
+def _launch_gemm(it):
+    ws = _ws(lib.dfm_gemm_workspace_size(it.desc), it.a.device)
+    it.desc.workspace_bytes = ws.numel() if ws is not None else 0
+    check(lib.dfm_gemm(it.dtype, it.desc, ptr(it.a), ptr(it.b), ptr(it.out), ptr(ws), stream()), "dfm_gemm")
+    if ACCOUNT is not None:
+        _acct(it.flops, it.nbytes, it.peak)
+
+
+def _launch_gemm_group(chunk):
+    """Up to 8 GEMMs of one dtype as one dfm_gemm_group launch."""
+    n = len(chunk)
+    descs = (_lib.GemmDesc * n)(*[it.desc for it in chunk])
+    pa = (ctypes.c_void_p * n)(*[it.a.data_ptr() for it in chunk])
+    pb = (ctypes.c_void_p * n)(*[it.b.data_ptr() for it in chunk])
+    pc = (ctypes.c_void_p * n)(*[it.out.data_ptr() for it in chunk])
+    ws = _ws(lib.dfm_gemm_group_workspace_size(n, descs), chunk[0].a.device)
+    descs[0].workspace_bytes = ws.numel() if ws is not None else 0
+    check(lib.dfm_gemm_group(chunk[0].dtype, n, descs, ctypes.cast(pa, ctypes.c_void_p), ctypes.cast(pb, ctypes.c_void_p),
+                             ctypes.cast(pc, ctypes.c_void_p), ptr(ws), stream()), "dfm_gemm_group")
+    if ACCOUNT is not None:
+        _acct(sum(it.flops for it in chunk), sum(it.nbytes for it in chunk), chunk[0].peak)
+
+
+def _launch_gemm_chunks(items):
+    for i in range(0, len(items), 8):
+        _launch_gemm_group(items[i:i + 8])
+
+
 def flush_wgrad(pending):
     """Issue queued GEMMs as grouped launches: problems of one dtype / operand layout, 8 per launch."""
     classes = {}
-    for item in pending:
-        d, dt = item[0], item[1]
-        classes.setdefault((dt, d.a_kcontig, d.b_kcontig), []).append(item)
-    for (dt, _, _), items in classes.items():
-        for i in range(0, len(items), 8):
-            chunk = items[i:i + 8]
-            n = len(chunk)
-            descs = (_lib.GemmDesc * n)(*[c[0] for c in chunk])
-            pa = (ctypes.c_void_p * n)(*[c[2].data_ptr() for c in chunk])
-            pb = (ctypes.c_void_p * n)(*[c[3].data_ptr() for c in chunk])
-            pc = (ctypes.c_void_p * n)(*[c[4].data_ptr() for c in chunk])
-            dev = chunk[0][2].device
-            ws = _ws(lib.dfm_gemm_group_workspace_size(n, descs), dev)
-            descs[0].workspace_bytes = ws.numel() if ws is not None else 0
-            check(lib.dfm_gemm_group(dt, n, descs, ctypes.cast(pa, ctypes.c_void_p), ctypes.cast(pb, ctypes.c_void_p),
-                                     ctypes.cast(pc, ctypes.c_void_p), ptr(ws), stream()), "dfm_gemm_group")
-            if ACCOUNT is not None:
-                _acct(sum(c[5] for c in chunk), sum(c[6] for c in chunk), chunk[0][7])
+    for it in pending:
+        classes.setdefault((it.dtype, it.desc.a_kcontig, it.desc.b_kcontig), []).append(it)
+    for items in classes.values():
+        _launch_gemm_chunks(items)
+
+
+def _flush(pending, reds):
+    if pending:
+        flush_wgrad(pending)
+    if reds:
+        flush_reductions(reds)
 
 
 def gemm(a, b, *, M, N, K, a_kcontig, b_kcontig, lda, ldb, out, ldc, batch=1, stride_a=0, stride_b=0,
@@ -227,19 +254,13 @@ def gemm(a, b, *, M, N, K, a_kcontig, b_kcontig, lda, ldb, out, ldc, batch=1, st
     byt += es * M * N * nb * ((preact is not None) + (mul is not None) + (res is not None) + 2 * (out2 is not None))
     byt += 4 * N * (bias is not None) + 4 * M * (colsum is not None)
     peak = "bf16" if a.dtype != torch.float32 else "f32"
+    it = _GemmItem(d, dt, a, b, out, 2.0 * M * N * K * nb, byt, peak, colsum, bias)
     if collect is not None:
-        collect.append((d, dt, a, b, out, 2.0 * M * N * K * nb, byt, peak))
-        return out
-    if defer and _WG_PENDING is not None and a.is_cuda:
-        # queued for the block's grouped launch; the tensors stay referenced until it is issued
-        _WG_PENDING.append((d, dt, a, b, out, 2.0 * M * N * K * nb, byt, peak, colsum, bias))
-        return out
-    nbytes = lib.dfm_gemm_workspace_size(d)
-    ws = _ws(nbytes, a.device)
-    d.workspace_bytes = ws.numel() if ws is not None else 0
-    check(lib.dfm_gemm(dt, d, ptr(a), ptr(b), ptr(out), ptr(ws), stream()), "dfm_gemm")
-    if ACCOUNT is not None:
-        _acct(2.0 * M * N * K * nb, byt, peak)
+        collect.append(it)
+    elif defer and _WG_PENDING is not None:
+        _WG_PENDING.append(it)  # for the block's grouped launch; the tensors stay referenced until it is issued
+    else:
+        _launch_gemm(it)
     return out
 
 
@@ -251,26 +272,9 @@ def gemm_many(calls):
     for c in calls:
         c(items)
     if len(items) == 1:
-        for d, dt, a, b, out, fl, by, peak in items:
-            ws = _ws(lib.dfm_gemm_workspace_size(d), a.device)
-            d.workspace_bytes = ws.numel() if ws is not None else 0
-            check(lib.dfm_gemm(dt, d, ptr(a), ptr(b), ptr(out), ptr(ws), stream()), "dfm_gemm")
-            if ACCOUNT is not None:
-                _acct(fl, by, peak)
-        return
-    for i in range(0, len(items), 8):
-        chunk = items[i:i + 8]
-        n = len(chunk)
-        descs = (_lib.GemmDesc * n)(*[c[0] for c in chunk])
-        pa = (ctypes.c_void_p * n)(*[c[2].data_ptr() for c in chunk])
-        pb = (ctypes.c_void_p * n)(*[c[3].data_ptr() for c in chunk])
-        pc = (ctypes.c_void_p * n)(*[c[4].data_ptr() for c in chunk])
-        ws = _ws(lib.dfm_gemm_group_workspace_size(n, descs), chunk[0][2].device)
-        descs[0].workspace_bytes = ws.numel() if ws is not None else 0
-        check(lib.dfm_gemm_group(chunk[0][1], n, descs, ctypes.cast(pa, ctypes.c_void_p), ctypes.cast(pb, ctypes.c_void_p),
-                                 ctypes.cast(pc, ctypes.c_void_p), ptr(ws), stream()), "dfm_gemm_group")
-        if ACCOUNT is not None:
-            _acct(sum(c[5] for c in chunk), sum(c[6] for c in chunk), chunk[0][7])
+        _launch_gemm(items[0])
+    else:
+        _launch_gemm_chunks(items)
 
 
 def linear(x, w, bias=None, *, act=0, preact=None, mul=None, res=None, colscale=None, rowscale=None,

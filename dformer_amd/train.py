@@ -17,7 +17,8 @@ import torch.nn as nn
 
 from . import kernels as K
 from .decoders import collectives_on
-from .functional import invalidate_weights, join_streams, register_grad_slot, register_shadow
+from .functional import invalidate_weights, register_grad_slot, register_shadow
+from .streams import join_streams
 
 
 def group_weight(module, norm_layer=nn.BatchNorm2d):

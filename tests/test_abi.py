@@ -42,7 +42,7 @@ def test_binding_signatures_match_header():
 
 def test_abi_version_and_error_path():
     from dformer_amd import _lib
-    assert _lib.lib.dfm_abi_version() == 13
+    assert _lib.lib.dfm_abi_version() == 13 == _lib.ABI_VERSION
     assert _lib.BUILD_TAG.startswith("default red="), _lib.BUILD_TAG
     # argument validation fails before touching the GPU
     st = _lib.lib.dfm_layernorm_fwd(0, 10, 100000, None, 0, None, None, 1e-6, None, 0, None, None, None)
@@ -50,6 +50,24 @@ def test_abi_version_and_error_path():
     assert b"unsupported" in _lib.lib.dfm_last_error() or b"null" in _lib.lib.dfm_last_error()
     with pytest.raises(RuntimeError):
         _lib.check(st, "dfm_layernorm_fwd")
+
+
+def test_loader_refuses_another_abi():
+    """The loader's ABI comparison: a library reporting another version is an ImportError naming the file
+    and both versions (its descriptors would be laid out differently); the built library passes."""
+    from dformer_amd import _lib
+
+    class Stub:
+        @staticmethod
+        def dfm_abi_version():
+            return 12
+
+    with pytest.raises(ImportError) as e:
+        _lib.check_abi(Stub)
+    msg = str(e.value)
+    assert "12" in msg and str(_lib.ABI_VERSION) in msg and _lib.LIB_PATH in msg
+    _lib.check_abi(_lib.lib)
+    _lib.check_abi(ctypes.CDLL(_lib.LIB_PATH))
 
 
 @pytest.mark.parametrize("cname,pyname", [("DfmGemmDesc", "GemmDesc"), ("DfmPartialSum", "PartialSum"),

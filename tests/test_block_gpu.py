@@ -66,7 +66,10 @@ def run_block(name, dtype):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", BLOCKS)
 def test_block_fp32_vs_reference_goldens(name):
-    g, blk, x, xe, y, ye, last = run_block(name, torch.float32)
+    fp32_golden_check(*run_block(name, torch.float32))
+
+
+def fp32_golden_check(g, blk, x, xe, y, ye, last):
     tol = 1e-3
     assert rel_err(y.cpu(), g["y"]) < tol
     assert rel_err(x.grad.cpu(), g["gx"]) < tol
@@ -156,3 +159,46 @@ def bf16_envelope_check(name, tag, g, y, ye, gx, gxe, grads, last):
             json.dump({"errs": errs, "ratios": ratios, "mult": BF16_ENV_MULT, "floor": BF16_FLOOR}, fh, indent=1)
     bad = {k: (errs[k], gate(k)) for k in errs if errs[k] >= gate(k)}
     assert not bad, bad
+
+
+WG_STREAM_BLOCKS = ["block_base_s2",       # 2x9x10x256, window 7: pooled branch and both ConvFFN forks
+                    "block_base_s0",       # 1x16x20x64, window 0
+                    "block_base_s3_last"]  # drop_depth: no ConvFFN fork
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("name", WG_STREAM_BLOCKS)
+def test_block_wgrad_stream_bit_equal(name, dtype, monkeypatch):
+    """Every weight-gradient group of the Block's backward on the weight-gradient stream
+    (kernels.WG_STREAM_MIN_FLOPS = 0; the goldens' groups are all below the default threshold) against none
+    there (inf): outputs, input gradients and every parameter gradient bit-equal, the stream used exactly in
+    the first run, and the first run within the golden gates of the tests above."""
+    from dformer_amd import kernels as Kk, streams
+    launched_on = []
+    check = Kk.check
+
+    def logged(status, what):
+        launched_on.append(torch.cuda.current_stream().cuda_stream)
+        return check(status, what)
+    monkeypatch.setattr(Kk, "check", logged)
+    runs = []
+    for min_flops in (0, float("inf")):
+        monkeypatch.setattr(Kk, "WG_STREAM_MIN_FLOPS", min_flops)
+        del launched_on[:]
+        g, blk, x, xe, y, ye, last = run = run_block(name, dtype)
+        wg = streams.side_stream(x.device, "wgrad").cuda_stream
+        assert (launched_on.count(wg) > 0) == (min_flops == 0), (min_flops, launched_on.count(wg), len(launched_on))
+        runs.append(run)
+    (g, blk0, x0, xe0, y0, ye0, last), (_, blk1, x1, xe1, y1, ye1, _) = runs
+    assert torch.equal(y0, y1) and torch.equal(ye0, ye1)
+    assert torch.equal(x0.grad, x1.grad) and torch.equal(xe0.grad, xe1.grad)
+    g0 = {k: p.grad for k, p in blk0.named_parameters() if p.grad is not None}
+    g1 = {k: p.grad for k, p in blk1.named_parameters() if p.grad is not None}
+    assert g0.keys() == g1.keys() and len(g0) > 0
+    differ = [k for k in g0 if not torch.equal(g0[k], g1[k])]
+    assert not differ, differ
+    if dtype == torch.float32:
+        fp32_golden_check(*runs[0])
+    else:
+        bf16_envelope_check(name, "wgstream", g, y0, ye0, x0.grad, xe0.grad, g0, last)

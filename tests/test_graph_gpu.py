@@ -34,10 +34,17 @@ def _build(decoder):
     return cfg, model
 
 
-@pytest.mark.parametrize("decoder", ["ham", "MLPDecoder"])
-def test_graphed_steps_match_eager(decoder):
+# wg_min: kernels.WG_STREAM_MIN_FLOPS for the case; at 0 every weight-gradient group runs on the
+# weight-gradient stream (Tiny at this size has none of >= 4 GFLOP), so the captured graph includes it
+@pytest.mark.parametrize("decoder,wg_min", [pytest.param("ham", None, id="ham"),
+                                            pytest.param("MLPDecoder", None, id="MLPDecoder"),
+                                            pytest.param("ham", 0, id="ham-wgstream")])
+def test_graphed_steps_match_eager(decoder, wg_min, monkeypatch):
     import bench
+    from dformer_amd import kernels as Kk
     from dformer_amd.train import FusedAdamW, GraphedTrainStep, train_step
+    if wg_min is not None:
+        monkeypatch.setattr(Kk, "WG_STREAM_MIN_FLOPS", wg_min)
     dev = torch.device("cuda", 0)
     cfg, ma = _build(decoder)   # same seed -> identical initial weights
     _, mb = _build(decoder)

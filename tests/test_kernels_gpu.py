@@ -1199,3 +1199,38 @@ def test_seg_loss_fwd_grad_fused(dt, B, h, w, H, W, ncls):
     assert torch.equal(out, out2) and torch.equal(dl, dl2)
     dl16 = k.seg_loss_bwd_gather(part, B, h, w, ncls, out, gs, dt)  # written in the logits dtype directly
     assert rel(dl16.float(), dl) < (1e-6 if dt == torch.float32 else 4e-3)
+
+
+def test_streams_roles_and_join(monkeypatch):
+    """streams.side_stream: one stream per (device, role). streams.join_streams(main): the current stream
+    waits once for `main` and once for every side stream of its device, never for itself."""
+    from dformer_amd import streams
+    dev = torch.device("cuda", torch.cuda.current_device())
+    side = {r: streams.side_stream(dev, r) for r in ("ffn", "attn_bwd", "wgrad")}
+    assert all(streams.side_stream(dev, r) is s for r, s in side.items())
+    assert len({s.cuda_stream for s in side.values()}) == 3
+    assert torch.cuda.current_stream().cuda_stream not in {s.cuda_stream for s in side.values()}
+    registered = sorted(s.cuda_stream for s in streams._STREAMS.values() if s.device == dev)
+    assert set(s.cuda_stream for s in side.values()) <= set(registered)
+    waits = []
+    wait = torch.cuda.Stream.wait_stream
+
+    def logged(self, other):
+        waits.append((self.cuda_stream, other.cuda_stream))
+        return wait(self, other)
+    monkeypatch.setattr(torch.cuda.Stream, "wait_stream", logged)
+    main = torch.cuda.Stream()
+    cur = torch.cuda.current_stream().cuda_stream
+    streams.join_streams(main)
+    assert sorted(waits) == sorted((cur, h) for h in registered + [main.cuda_stream])
+    del waits[:]
+    with torch.cuda.stream(side["wgrad"]):  # a registered stream as the current one: not waited for
+        streams.join_streams(main)
+    me = side["wgrad"].cuda_stream
+    assert sorted(waits) == sorted((me, h) for h in registered + [main.cuda_stream] if h != me)
+    del waits[:]
+    with torch.cuda.stream(main):  # main as the current stream, and no main at all
+        streams.join_streams(main)
+        streams.join_streams()
+    assert sorted(waits) == sorted([(main.cuda_stream, h) for h in registered] * 2)
+    torch.cuda.synchronize()

@@ -112,7 +112,7 @@ def test_slide_msf_accumulate_null_pointer_wins_nothing_over_dtype():
     args[0] = 7
     assert _lib.lib.dfm_slide_msf_accumulate(*args) == -2
     assert b"dfm_slide_msf_accumulate: unsupported dtype 7" in _lib.lib.dfm_last_error()
-    assert _lib.lib.dfm_abi_version() == 13  # a new symbol, no layout change
+    assert _lib.lib.dfm_abi_version() == 13 == _lib.ABI_VERSION  # a new symbol, no layout change
 
 
 def test_python_wrapper_checks_buffer_sizes():
