@@ -14,10 +14,18 @@ int(`config.eval_stride_rate` * crop); the crops run through the model in stacks
 logits land in one [G*B*h*w, ncls] buffer, and one kernel (`K.slide_msf_accumulate`) gathers, per
 label pixel, the covering windows' upsampled logits, averages them, and does the flip back, the
 resize to the label size, the softmax and the accumulation as above; no zero-padded full-size
-logits, sum or count map is materialised. Prediction PNG export (`save_dir`) is not on the path
-and raises.
+logits, sum or count map is materialised. `evaluate_msf` exports no prediction images (`save_dir`
+raises).
+
+Single-scale evaluation (val_mm.py:102-207 `evaluate`, the reference training loop's default) and
+prediction export (`evaluate(save_dir=...)`, val_mm.py:25-98 `save_preds`): one forward per batch at
+the native size; `K.seg_predict` turns the decoder's low-res logits straight into the uint8 class
+map and the confusion histogram (the argmax of the four-tap interpolation; the softmax is monotone),
+so no full-resolution logits, scores or permuted copies exist. With `sliding=True` the window-averaged
+logits of `slide_inference` are rows already and go through `update_rows` / `K.rows_argmax`.
 """
 import math
+import os
 
 import torch
 
@@ -50,6 +58,19 @@ class Metrics:
         """pred: [B, ncls, H, W] class scores (any layout), target: [B, H, W]."""
         rows = pred.float().permute(0, 2, 3, 1).contiguous().view(-1, pred.shape[1])
         self.update_rows(rows, target)
+
+    def update_low(self, low_rows, shape, target, pred=None):
+        """The fused update from the decoder's low-res logits: low_rows [B*h*w, >= ncls] NHWC rows,
+        shape = (B, h, w), target [B, H, W]. Equals update(F.interpolate(low, (H, W), 'bilinear',
+        align_corners=False), target) without materialising the upsampled logits; pred (uint8
+        [B, H, W], optional) receives the class map."""
+        B, h, w = shape
+        if target.dim() != 3 or target.shape[0] != B:
+            raise ValueError(f"update_low: target {tuple(target.shape)} is not [{B}, H, W]")
+        self.index += 1
+        K.seg_predict(low_rows, B, h, w, self.num_classes, tuple(target.shape[1:]), pred=pred,
+                      label=target.long().contiguous(), ignore=self.ignore_label, hist=self._hist)
+        return pred
 
     def compute_iou(self):
         h = self.hist
@@ -207,3 +228,129 @@ def evaluate_msf(model, dataloader, config, device, scales, flip, engine=None, s
         torch.distributed.all_gather_object(all_metrics, metrics)
         return all_metrics
     return metrics
+
+
+def pred_png_name(fn):
+    """val_mm.py:161-167: the path of a prediction image below save_dir, without the "_pred.png"."""
+    return fn.replace(".jpg", "").replace(".png", "").replace("datasets/", "")
+
+
+def pred_img_id(rgb_path):
+    """val_mm.py:89: the last path component with leading and trailing '.', 'j', 'p', 'g' characters
+    removed (str.strip('.jpg') strips a character set, not a suffix; the reference's file names are
+    the contract)."""
+    return rgb_path.split("/")[-1].strip(".jpg")
+
+
+def check_palette(palette, num_classes):
+    """The caller's colour table as a uint8 [>= num_classes, 3] numpy array."""
+    import numpy as np
+    pal = palette.detach().cpu().numpy() if isinstance(palette, torch.Tensor) else np.asarray(palette)
+    if pal.ndim != 2 or pal.shape[1] != 3 or pal.shape[0] < num_classes:
+        raise ValueError(f"palette of shape {pal.shape} is not [>= {num_classes}, 3]")
+    if pal.dtype != np.uint8:
+        if not np.issubdtype(pal.dtype, np.integer) or pal.min() < 0 or pal.max() > 255:
+            raise ValueError(f"palette values must be integers in [0, 255], got {pal.dtype}")
+        pal = pal.astype(np.uint8)
+    return pal
+
+
+def _optional(config, name):
+    try:  # a dict-backed config raises KeyError for a missing name
+        return getattr(config, name)
+    except (AttributeError, KeyError):
+        return None
+
+
+def _write_pred_png(path, pred, palette):
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise ImportError("evaluate(save_dir=...) writes PNG files with Pillow (PIL), which is not installed") from e
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    Image.fromarray(pred if palette is None else palette[pred]).save(path)
+
+
+def _batch_inputs(batch, device):
+    """val_mm.py:41-52, 115-125: rgb, depth ('laser', the reference's key here, else 'modal_x') and gt of
+    a batch on the device; an unbatched sample gets its batch axis."""
+    rgb, gt = batch["rgb"], batch["gt"]
+    modal_x = batch["laser"] if "laser" in batch else batch["modal_x"]
+    if rgb.dim() == 3:
+        rgb = rgb.unsqueeze(0)
+    if modal_x.dim() == 3:
+        modal_x = modal_x.unsqueeze(0)
+    if gt.dim() == 2:
+        gt = gt.unsqueeze(0)
+    return rgb.to(device), modal_x.to(device), gt.to(device)
+
+
+def _update_batch(model, metrics, rgb, modal_x, gt, config, sliding, want_pred):
+    """One batch of evaluate / save_preds: the histogram update and, when asked for, the uint8 class map
+    [B, H, W] (on the device)."""
+    ncls = config.num_classes
+    if sliding:
+        scores = slide_inference(model, rgb, modal_x, config, _optional(config, "eval_crop_batch"))
+        if tuple(scores.shape[-2:]) != tuple(gt.shape[-2:]):
+            raise ValueError(f"evaluate: sliding-window predictions {tuple(scores.shape[-2:])} do not match the "
+                             f"labels {tuple(gt.shape[-2:])}")
+        rows = scores.permute(0, 2, 3, 1).reshape(-1, ncls)  # the NHWC rows behind slide_inference's view
+        metrics.update_rows(rows, gt)
+        return K.rows_argmax(rows, ncls).view(gt.shape) if want_pred else None
+    if tuple(gt.shape[-2:]) != tuple(rgb.shape[-2:]):
+        raise ValueError(f"evaluate: labels {tuple(gt.shape[-2:])} do not match the image {tuple(rgb.shape[-2:])}")
+    rows, shape = _nhwc_rows(model._low_logits(rgb, modal_x))
+    pred = torch.empty(gt.shape, device=rows.device, dtype=torch.uint8) if want_pred else None
+    return metrics.update_low(rows, shape, gt, pred=pred)
+
+
+def _gathered(metrics, engine):
+    if engine is not None and getattr(engine, "distributed", False):
+        all_metrics = [None for _ in range(engine.world_size)]
+        torch.distributed.all_gather_object(all_metrics, metrics)
+        return all_metrics
+    return metrics
+
+
+@torch.no_grad()
+def evaluate(model, dataloader, config, device, engine=None, save_dir=None, sliding=False, palette=None):
+    """val_mm.py:102-207. dataloader yields dicts with 'rgb', 'laser' (or 'modal_x'), 'gt' and, for
+    save_dir, 'fn'. Returns the Metrics (a list of every rank's Metrics when engine.distributed).
+    save_dir writes <save_dir>/<name>_pred.png for every image of a batch: coloured with `palette`
+    (else config.palette; uint8 [>= num_classes, 3], the caller's data) or, without one, the class
+    indices as an 8-bit image."""
+    if sliding:
+        slide_strides(tuple(config.eval_crop_size), config.eval_stride_rate)  # a bad rate fails before the first batch
+    if save_dir is not None:
+        if palette is None:
+            palette = _optional(config, "palette")
+        if palette is not None:
+            palette = check_palette(palette, config.num_classes)
+    model.eval()
+    metrics = Metrics(config.num_classes, config.background, device)
+    for batch in dataloader:
+        rgb, modal_x, gt = _batch_inputs(batch, device)
+        pred = _update_batch(model, metrics, rgb, modal_x, gt, config, sliding, save_dir is not None)
+        if save_dir is not None:
+            for p, fn in zip(pred.cpu().numpy(), batch["fn"]):
+                _write_pred_png(os.path.join(save_dir, pred_png_name(fn) + "_pred.png"), p, palette)
+    return _gathered(metrics, engine)
+
+
+@torch.no_grad()
+def save_preds(model, dataloader, config, device, engine=None, model_path=None, sliding=False, out_root="output"):
+    """val_mm.py:25-98: the metrics of `evaluate` plus one <out_root>/<model_path>/<img_id>.npy uint8 class
+    map per image, img_id from batch['rgb_path'][i] (pred_img_id)."""
+    import numpy as np
+    if sliding:
+        slide_strides(tuple(config.eval_crop_size), config.eval_stride_rate)
+    out_dir = os.path.join(out_root, str(model_path))
+    os.makedirs(out_dir, exist_ok=True)
+    model.eval()
+    metrics = Metrics(config.num_classes, config.background, device)
+    for batch in dataloader:
+        rgb, modal_x, gt = _batch_inputs(batch, device)
+        pred = _update_batch(model, metrics, rgb, modal_x, gt, config, sliding, True)
+        for p, path in zip(pred.cpu().numpy(), batch["rgb_path"]):
+            np.save(os.path.join(out_dir, pred_img_id(path) + ".npy"), p)
+    return _gathered(metrics, engine)

@@ -918,6 +918,50 @@ def seg_confusion(acc, label, ncls, ignore, hist):
     return hist
 
 
+def seg_predict(low_rows, B, h, w, ncls, out_hw, pred=None, label=None, ignore=255, hist=None):
+    """argmax over classes of the align_corners=False upsampling of the low-res logits low_rows
+    [B*h*w, >= ncls] to out_hw, without materialising it (builder.py:203 + val_mm.py:129-132).
+    pred: uint8 [B, H, W] to fill; None allocates it, unless a label is given: then only the histogram
+    is computed. With label [B, H, W] int64, hist [ncls*ncls] int64 += bincount(label*ncls + argmax)
+    over label != ignore. Returns pred (hist when there is no pred)."""
+    H, W = out_hw
+    if low_rows.dim() != 2 or low_rows.shape[0] < B * h * w or low_rows.shape[1] < ncls:
+        raise ValueError(f"seg_predict: low rows {tuple(low_rows.shape)} do not hold {B} x {h} x {w} x {ncls}")
+    if (label is None) != (hist is None):
+        raise ValueError("seg_predict: label and hist go together")
+    if label is not None:
+        if label.dtype != torch.int64 or not label.is_contiguous() or label.numel() != B * H * W:
+            raise ValueError(f"seg_predict: label {tuple(label.shape)} {label.dtype} is not contiguous int64 "
+                             f"[{B}, {H}, {W}]")
+        if hist.dtype != torch.int64 or not hist.is_contiguous() or hist.numel() != ncls * ncls:
+            raise ValueError(f"seg_predict: hist {tuple(hist.shape)} {hist.dtype} is not contiguous int64 "
+                             f"[{ncls}*{ncls}]")
+    if pred is None and label is None:
+        pred = torch.empty(B, H, W, device=low_rows.device, dtype=torch.uint8)
+    if pred is not None and (pred.dtype != torch.uint8 or not pred.is_contiguous() or pred.numel() != B * H * W):
+        raise ValueError(f"seg_predict: pred {tuple(pred.shape)} {pred.dtype} is not contiguous uint8 [{B}, {H}, {W}]")
+    check(lib.dfm_seg_predict(dtype_code(low_rows), B, h, w, ncls, ptr(low_rows), ld(low_rows), H, W, ptr(pred),
+                              ptr(label), ignore, ptr(hist), stream()), "dfm_seg_predict")
+    if ACCOUNT is not None:
+        npix = B * H * W
+        _acct(0, B * h * w * ncls * _es(low_rows) + npix * ((pred is not None) + 8 * (label is not None)))
+    return pred if pred is not None else hist
+
+
+def rows_argmax(acc, ncls, out=None):
+    """uint8 [rows] = argmax over the ncls float32 scores of each row of acc (first maximum)."""
+    if acc.dim() != 2 or acc.shape[1] != ncls or acc.dtype != torch.float32 or not acc.is_contiguous():
+        raise ValueError(f"rows_argmax: scores {tuple(acc.shape)} {acc.dtype} are not contiguous float32 [*, {ncls}]")
+    if out is None:
+        out = torch.empty(acc.shape[0], device=acc.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != acc.shape[0]:
+        raise ValueError(f"rows_argmax: out {tuple(out.shape)} {out.dtype} is not contiguous uint8 [{acc.shape[0]}]")
+    check(lib.dfm_rows_argmax(acc.shape[0], ncls, ptr(acc), ptr(out), stream()), "dfm_rows_argmax")
+    if ACCOUNT is not None:
+        _acct(0, acc.numel() * 4 + acc.shape[0])
+    return out
+
+
 # ---------------------------------------------------------------------------------------- NMF
 def _copy_dtype(flag):
     """bf16_copy argument: False / None (no copy), True (bf16) or a 16-bit torch dtype."""

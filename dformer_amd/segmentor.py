@@ -84,6 +84,14 @@ class EncoderDecoder(nn.Module):
         low = self._low_logits(rgb, modal_x)
         return self._upsample(low, rgb.shape[-2:])
 
+    @torch.no_grad()
+    def predict(self, rgb, modal_x):
+        """The class map of the eval forward, uint8 [B, H, W]: forward(rgb, modal_x).argmax(1) without the
+        full-resolution logits (one fused upsample + argmax kernel over the low-res logits)."""
+        rows, (B, h, w) = _nhwc_rows(self._low_logits(rgb, modal_x))
+        K.TAG = "eval"
+        return K.seg_predict(rows, B, h, w, rows.shape[1], tuple(rgb.shape[-2:]))
+
     def forward(self, rgb, modal_x=None, label=None):
         low = self._low_logits(rgb, modal_x)
         if label is None:

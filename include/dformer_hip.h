@@ -443,6 +443,22 @@ int dfm_seg_confusion(long npix, int ncls, const float* acc, const long long* la
 int dfm_slide_msf_accumulate(int dtype, int B, int h, int w, int ncls, const void* low, long ldl, int hc, int wc,
                              int hstride, int wstride, int Hs, int Ws, int H, int W, int flip, int softmax,
                              float* acc, dfm_stream_t stream);
+/* Single-scale evaluation and prediction export (utils/val_mm.py:102-207 evaluate, 25-98 save_preds).
+ * New symbols only: dfm_abi_version() stays 13.
+ * seg_predict: replaces F.interpolate(low, (H, W), 'bilinear', align_corners=False) (builder.py:203) ->
+ *   softmax(1) -> argmax(1) (val_mm.py:129-132, 169) -> Metrics.update (metrics_new.py:16-20) in one pass.
+ *   low [B*h*w][ldl] holds the decoder's low-res logits (NHWC rows, ldl >= ncls). For every output pixel
+ *   pred[b][y][x] (uint8, [B][H][W]) = the first maximum over c < ncls of the interpolated logit (fp32; the
+ *   softmax is monotone and skipped; ties go to the lowest class, like torch.argmax), and, with a label
+ *   [B][H][W] int64, hist [ncls*ncls] uint64 += 1 at [t * ncls + pred] for t != ignore within [0, ncls).
+ *   pred may be NULL; label and hist are given together or both NULL; one output at least. Nothing of
+ *   size [B, ncls, H, W] is materialised. Needs 1 <= ncls <= 64, h <= H, w <= W (upsampling).
+ * rows_argmax: pred[p] (uint8) = the first maximum of the float32 score row acc[p][0 .. ncls), the
+ *   preds.argmax(dim=1) of val_mm.py:84,169 for scores that already exist as NHWC rows (sliding windows). */
+int dfm_seg_predict(int dtype, int B, int h, int w, int ncls, const void* low, long ldl, int H, int W,
+                    unsigned char* pred, const long long* label, int ignore, unsigned long long* hist,
+                    dfm_stream_t stream);
+int dfm_rows_argmax(long npix, int ncls, const float* acc, unsigned char* pred, dfm_stream_t stream);
 
 /* ---------------------------------------------------------------- NMF2D multiplicative update
  * ham_head.py:120-145:  out = a * num / (den + eps)  (float32), and its backward:
