@@ -9,14 +9,16 @@
 //                       390-392) composed per output pixel: 16 low-res taps, nothing materialised
 //   dfm_slide_msf_accumulate  the same with sliding-window inference (val_mm.py:257-322): the scaled
 //                       logits are the per-pixel average of the overlapping windows' upsampled
-//                       logits, gathered from every window's low-res logits
+//                       logits, gathered from every window's low-res logits. One kernel serves both:
+//                       dfm_msf_accumulate is its case of one window that covers the scaled image
 //   dfm_seg_confusion   hist[t * ncls + argmax_c acc[p, c]] += 1 over pixels with t != ignore
 // and single-scale evaluation (utils/val_mm.py:102-207 evaluate, 25-98 save_preds):
 //   dfm_seg_predict     pred[b, y, x] = argmax_c of the model's own upsampling (builder.py:203) of the
 //                       low-res logits, and the confusion histogram of it, in one pass: a workgroup
 //                       stages the low-res patch under its rectangle of output pixels in LDS; neither
 //                       the full-resolution logits nor their softmax (monotone) exist anywhere
-//   dfm_rows_argmax     pred[p] = argmax_c acc[p, c] of score rows (the sliding-window results)
+//   dfm_rows_argmax     pred[p] = argmax_c acc[p, c] of score rows (the sliding-window results); the
+//                       same kernel as dfm_seg_confusion, which counts the argmax instead of storing it
 // Every output element is owned by one thread (no float atomics); the histograms use integer
 // atomics, so all of them are deterministic.
 #include <algorithm>
@@ -70,63 +72,14 @@ __global__ __launch_bounds__(kThreads) void resize_nchw_kernel(int B, int C, int
   }
 }
 
-template <typename T, int NC>
-__global__ __launch_bounds__(kThreads) void msf_accumulate_kernel(int B, int h, int w, int ncls,
-                                                                  const T* __restrict__ low, long ldl, int Hs, int Ws,
-                                                                  int H, int W, int flip, float* __restrict__ acc) {
-  const long n = (long)B * H * W;
-  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < n; p += (long)gridDim.x * blockDim.x) {
-    const int x = (int)(p % W);
-    const long t = p / W;
-    const int y = (int)(t % H);
-    const long b = t / H;
-    float z[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) z[c] = 0.f;
-    const Lin sy = lin_src(y, Hs, H, true), sx = lin_src(x, Ws, W, true);
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int ys = (a >> 1) ? sy.i1 : sy.i0;
-      const int xs0 = (a & 1) ? sx.i1 : sx.i0;
-      const float wa = ((a >> 1) ? sy.l1 : sy.l0) * ((a & 1) ? sx.l1 : sx.l0);
-      const int xs = flip ? Ws - 1 - xs0 : xs0;
-      const Lin ly = lin_src(ys, h, Hs, false), lx = lin_src(xs, w, Ws, false);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int yl = (q >> 1) ? ly.i1 : ly.i0, xl = (q & 1) ? lx.i1 : lx.i0;
-        const float wq = wa * ((q >> 1) ? ly.l1 : ly.l0) * ((q & 1) ? lx.l1 : lx.l0);
-        const T* src = low + ((b * h + yl) * w + xl) * ldl;
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-          if (c < ncls) z[c] = fmaf(wq, ldf(src + c), z[c]);
-      }
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-      if (c < ncls) mx = fmaxf(mx, z[c]);
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-      if (c < ncls) {
-        z[c] = expf(z[c] - mx);
-        s += z[c];
-      }
-    const float inv = 1.f / s;
-    float* dst = acc + p * ncls;
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-      if (c < ncls) dst[c] += z[c] * inv;
-  }
-}
-
-// Sliding-window form (val_mm.py:257-322 slide_inference inside evaluate_msf): the scaled image is
-// covered by hg x wg windows of hc x wc pixels, window (gi, gj) starting at
-// (win_start(gi, hstride, hc, Hs), win_start(gj, wstride, wc, Ws)); low holds every window's low-res
-// logits, [hg*wg][B][h][w] rows. Per output pixel the 4 align_corners=True taps of the scaled grid are
-// each the average over the covering windows (ascending (gi, gj), summed then divided by the count,
-// like the reference's preds / count_mat) of that window's align_corners=False upsampling at the
-// tap: nothing of size [B, ncls, Hs, Ws] is materialised.
+// The accumulate kernel, in its sliding-window form (val_mm.py:257-322 slide_inference inside
+// evaluate_msf): the scaled image is covered by hg x wg windows of hc x wc pixels, window (gi, gj)
+// starting at (win_start(gi, hstride, hc, Hs), win_start(gj, wstride, wc, Ws)); low holds every window's
+// low-res logits, [hg*wg][B][h][w] rows. Per output pixel the 4 align_corners=True taps of the scaled
+// grid are each the average over the covering windows (ascending (gi, gj), summed then divided by the
+// count, like the reference's preds / count_mat) of that window's align_corners=False upsampling at the
+// tap: nothing of size [B, ncls, Hs, Ws] is materialised. Plain multi-scale evaluation
+// (dfm_msf_accumulate) is its one-window case: crop = stride = (Hs, Ws), hg = wg = 1, count 1.
 DFM_INLINE int win_start(int g, int stride, int crop, int n) { return max(min(g * stride + crop, n) - crop, 0); }
 
 // kSlideLanes lanes share an output pixel: lane j owns classes j, j + kSlideLanes, ..., so a group's
@@ -216,33 +169,6 @@ __global__ __launch_bounds__(kThreads) void slide_msf_accumulate_kernel(
     for (int k = 0; k < KC; ++k)
       if (j + k * L < ncls) dst[k * L] += z[k] * inv;
   }
-}
-
-__global__ __launch_bounds__(kThreads) void confusion_kernel(long npix, int ncls, const float* __restrict__ acc,
-                                                             const long long* __restrict__ label, int ignore,
-                                                             unsigned long long* __restrict__ hist) {
-  extern __shared__ unsigned int lh[];
-  const int nb = ncls * ncls;
-  for (int i = threadIdx.x; i < nb; i += blockDim.x) lh[i] = 0u;
-  __syncthreads();
-  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < npix; p += (long)gridDim.x * blockDim.x) {
-    const long long t = label[p];
-    if (t == ignore || t < 0 || t >= ncls) continue;
-    const float* a = acc + p * ncls;
-    int best = 0;
-    float bv = a[0];
-    for (int c = 1; c < ncls; ++c) {
-      const float v = a[c];
-      if (v > bv) {  // first maximum wins, like torch.argmax
-        bv = v;
-        best = c;
-      }
-    }
-    atomicAdd(&lh[t * ncls + best], 1u);
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < nb; i += blockDim.x)
-    if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
 }
 
 // ---- dfm_seg_predict. A workgroup owns kPredTY x kPredTX output pixels of one image; thread t owns
@@ -361,12 +287,21 @@ __global__ __launch_bounds__(kThreads) void seg_predict_kernel(int h, int w, int
   }
 }
 
-// kSlideLanes lanes share a row of scores (contiguous loads); the group's (value, class) pairs reduce to
-// the first maximum
+// The row argmax of dfm_rows_argmax (pred) and dfm_seg_confusion (label, ignore, hist; ncls * ncls
+// counters of LDS): kSlideLanes lanes share a row of scores (contiguous loads); the group's (value, class)
+// pairs reduce to the first maximum, which lane 0 stores and / or counts into the workgroup's histogram;
+// the workgroup flushes its counters once.
 __global__ __launch_bounds__(kThreads) void rows_argmax_kernel(long npix, int ncls, const float* __restrict__ acc,
-                                                               unsigned char* __restrict__ pred) {
+                                                               unsigned char* __restrict__ pred,
+                                                               const long long* __restrict__ label, int ignore,
+                                                               unsigned long long* __restrict__ hist) {
+  extern __shared__ unsigned int lh[];
   constexpr int L = kSlideLanes, kPix = kThreads / L;
   const int j = threadIdx.x % L;
+  if (label) {
+    for (int i = threadIdx.x; i < ncls * ncls; i += kThreads) lh[i] = 0u;
+    __syncthreads();
+  }
   // a group's lanes share p, so they leave the loop together and the cross-lane steps stay inside it
   for (long p = blockIdx.x * (long)kPix + threadIdx.x / L; p < npix; p += (long)gridDim.x * kPix) {
     const float* a = acc + p * ncls;
@@ -392,30 +327,23 @@ __global__ __launch_bounds__(kThreads) void rows_argmax_kernel(long npix, int nc
         best = ob;
       }
     }
-    if (j == 0) pred[p] = (unsigned char)best;
+    if (j != 0) continue;
+    if (pred) pred[p] = (unsigned char)best;
+    if (label) {
+      const long long t = label[p];
+      if (t != ignore && t >= 0 && t < ncls) atomicAdd(&lh[t * ncls + best], 1u);
+    }
+  }
+  if (label) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < ncls * ncls; i += kThreads)
+      if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
   }
 }
 
 unsigned grid_for(long n, long cap = 16384) {
   const long g = (n + kThreads - 1) / kThreads;
   return (unsigned)(g < cap ? (g < 1 ? 1 : g) : cap);
-}
-
-template <typename T>
-int msf_typed(int B, int h, int w, int ncls, const void* low, long ldl, int Hs, int Ws, int H, int W, int flip,
-              float* acc, hipStream_t s) {
-  const unsigned g = grid_for((long)B * H * W);
-  if (ncls <= 16)
-    DFM_LAUNCH((msf_accumulate_kernel<T, 16>), dim3(g), dim3(kThreads), 0, s, B, h, w, ncls, (const T*)low, ldl, Hs,
-               Ws, H, W, flip, acc);
-  else if (ncls <= 40)
-    DFM_LAUNCH((msf_accumulate_kernel<T, 40>), dim3(g), dim3(kThreads), 0, s, B, h, w, ncls, (const T*)low, ldl, Hs,
-               Ws, H, W, flip, acc);
-  else
-    DFM_LAUNCH((msf_accumulate_kernel<T, kMaxCls>), dim3(g), dim3(kThreads), 0, s, B, h, w, ncls, (const T*)low, ldl,
-               Hs, Ws, H, W, flip, acc);
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
 }
 
 int slide_grids(int n, int crop, int stride) {  // val_mm.py:295-296
@@ -501,7 +429,9 @@ extern "C" int dfm_msf_accumulate(int dtype, int B, int h, int w, int ncls, cons
                 "dfm_msf_accumulate: bad argument");
   DFM_CHECK_ARG(ncls > 0 && ncls <= kMaxCls, "dfm_msf_accumulate: ncls=%d outside [1, %d]", ncls, kMaxCls);
   hipStream_t s = (hipStream_t)stream;
-  DFM_DTYPE_SWITCH(dtype, T, return msf_typed<T>(B, h, w, ncls, low, ldl, Hs, Ws, H, W, flip, acc, s));
+  // one window that covers the scaled image
+  DFM_DTYPE_SWITCH(dtype, T,
+                   return slide_msf_typed<T>(B, h, w, ncls, low, ldl, Hs, Ws, Hs, Ws, Hs, Ws, H, W, flip, 1, acc, s));
 }
 
 extern "C" int dfm_slide_msf_accumulate(int dtype, int B, int h, int w, int ncls, const void* low, long ldl, int hc,
@@ -531,8 +461,9 @@ extern "C" int dfm_seg_confusion(long npix, int ncls, const float* acc, const lo
   if (npix == 0) return DFM_OK;
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)ncls * ncls * sizeof(unsigned int);
-  DFM_LAUNCH(confusion_kernel, dim3(grid_for(npix, 2048)), dim3(kThreads), lds, s, npix, ncls, acc, label, ignore,
-             hist);
+  // a smaller grid than dfm_rows_argmax's: every workgroup flushes ncls * ncls counters
+  DFM_LAUNCH(rows_argmax_kernel, dim3(grid_for(npix * kSlideLanes, 2048)), dim3(kThreads), lds, s, npix, ncls, acc,
+             (unsigned char*)nullptr, label, ignore, hist);
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
@@ -559,7 +490,8 @@ extern "C" int dfm_rows_argmax(long npix, int ncls, const float* acc, unsigned c
   DFM_CHECK_ARG(npix >= 0, "dfm_rows_argmax: bad argument");
   if (npix == 0) return DFM_OK;
   hipStream_t s = (hipStream_t)stream;
-  DFM_LAUNCH(rows_argmax_kernel, dim3(grid_for(npix * kSlideLanes)), dim3(kThreads), 0, s, npix, ncls, acc, pred);
+  DFM_LAUNCH(rows_argmax_kernel, dim3(grid_for(npix * kSlideLanes)), dim3(kThreads), 0, s, npix, ncls, acc, pred,
+             (const long long*)nullptr, 0, (unsigned long long*)nullptr);
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }

@@ -1,36 +1,26 @@
 """Multi-scale + flip evaluation and mIoU metrics on the HIP path.
 
-Mirrors the reference's `utils/val_mm.py:325-472 evaluate_msf` and `utils/metrics_new.py:6-47
-Metrics` (same names, arguments and results). Per batch and scale s the inputs are resized to
-ceil(s*H/32)*32 x ceil(s*W/32)*32 (bilinear, align_corners=True) [and flipped], the model runs its
-eval forward (ham head: 7 NMF steps), and one kernel folds the model's own logits upsampling
-(align_corners=False), the flip back, the resize to the label size (align_corners=True), the
-softmax and the accumulation over scales into a float32 [B*H*W, ncls] buffer; the confusion
-histogram is another kernel.
-
-Sliding-window inference (val_mm.py:257-322 `slide_inference`, `evaluate_msf(..., sliding=True)`):
-the scaled image is cut into overlapping crops of `config.eval_crop_size` at a stride of
-int(`config.eval_stride_rate` * crop); the crops run through the model in stacks, their low-res
-logits land in one [G*B*h*w, ncls] buffer, and one kernel (`K.slide_msf_accumulate`) gathers, per
-label pixel, the covering windows' upsampled logits, averages them, and does the flip back, the
-resize to the label size, the softmax and the accumulation as above; no zero-padded full-size
-logits, sum or count map is materialised. `evaluate_msf` exports no prediction images (`save_dir`
-raises).
-
-Single-scale evaluation (val_mm.py:102-207 `evaluate`, the reference training loop's default) and
-prediction export (`evaluate(save_dir=...)`, val_mm.py:25-98 `save_preds`): one forward per batch at
-the native size; `K.seg_predict` turns the decoder's low-res logits straight into the uint8 class
-map and the confusion histogram (the argmax of the four-tap interpolation; the softmax is monotone),
-so no full-resolution logits, scores or permuted copies exist. With `sliding=True` the window-averaged
-logits of `slide_inference` are rows already and go through `update_rows` / `K.rows_argmax`.
+The reference's `utils/val_mm.py` (`evaluate_msf` 325-472, `slide_inference` 257-322, `evaluate`
+102-207, `save_preds` 25-98) and `utils/metrics_new.py:6-47 Metrics`, same names, arguments and
+results. Everything after the model works on the decoder's low-res logits as NHWC rows:
+- `evaluate_msf`: per scale [and flip] one kernel folds the model's upsampling (align_corners=False),
+  the flip back, the resize to the label size (align_corners=True), the softmax and the sum over
+  scales into a float32 [B*H*W, ncls] buffer. With `sliding=True` the scaled image is cut into crops
+  of `config.eval_crop_size` at a stride of int(`config.eval_stride_rate` * crop), the crops run
+  through the model in stacks, and the same kernel averages the covering windows per label pixel.
+  `save_dir` raises.
+- `evaluate` / `save_preds`: `K.seg_predict` turns the low-res logits into the uint8 class map and
+  the confusion histogram; with `sliding=True` the window-averaged logits go through `update_rows` /
+  `K.rows_argmax`.
+No full-resolution logits, zero-padded windows, sum or count maps are materialised.
 """
+import collections
 import math
 import os
 
 import torch
 
 from . import kernels as K
-from .decoders import _nhwc_rows
 
 
 class Metrics:
@@ -127,23 +117,44 @@ def slide_strides(crop_size, stride_rate):
     return strides
 
 
-def _slide_low_rows(model, x, e, crop_size, strides, crop_batch):
+def _optional(config, name):
+    try:  # a dict-backed config raises KeyError for a missing name
+        return getattr(config, name)
+    except (AttributeError, KeyError):
+        return None
+
+
+# the crop (hc, wc), its strides (slide_strides) and the most images per model call (None: one window of the batch)
+_Slide = collections.namedtuple("_Slide", "crop strides crop_batch")
+
+
+def _slide_config(config, crop_size=None, stride_rate=None, crop_batch=None):
+    """The validated sliding-window settings: config's eval_crop_size, eval_stride_rate and (optional)
+    eval_crop_batch, or, without a config, the arguments."""
+    if config is not None:
+        crop_size, stride_rate = config.eval_crop_size, config.eval_stride_rate
+        crop_batch = _optional(config, "eval_crop_batch")
+    crop = tuple(int(c) for c in crop_size)
+    return _Slide(crop, slide_strides(crop, stride_rate), crop_batch)
+
+
+def _slide_low_rows(model, x, e, slide):
     """The low-res logits of every sliding window of the scaled (and flipped) inputs x, e:
     ([G*B*h*w, ncls] rows, window-major, (B, h, w), (Hs, Ws) of the image the windows were cut from)."""
-    hc, wc = crop_size
+    hc, wc = slide.crop
     if hc > x.shape[2] or wc > x.shape[3]:  # val_mm.py:280-286: both dimensions go to the crop size
         x = K.resize_nchw(x, (hc, wc), True)
         e = K.resize_nchw(e, (hc, wc), True)
     B, _, Hs, Ws = x.shape
-    wins = [(y1, y2, x1, x2) for y1, y2 in slide_windows(Hs, hc, strides[0])
-            for x1, x2 in slide_windows(Ws, wc, strides[1])]
-    per = max(1, (crop_batch if crop_batch is not None else B) // B)  # whole windows per model call
+    wins = [(y1, y2, x1, x2) for y1, y2 in slide_windows(Hs, hc, slide.strides[0])
+            for x1, x2 in slide_windows(Ws, wc, slide.strides[1])]
+    per = max(1, (slide.crop_batch if slide.crop_batch is not None else B) // B)  # whole windows per model call
     buf, shape, off = None, None, 0
     for i in range(0, len(wins), per):
         chunk = wins[i:i + per]
         cx = torch.cat([x[:, :, y1:y2, x1:x2] for y1, y2, x1, x2 in chunk], 0)
         ce = torch.cat([e[:, :, y1:y2, x1:x2] for y1, y2, x1, x2 in chunk], 0)
-        rows, (b, h, w) = _nhwc_rows(model._low_logits(cx, ce))
+        rows, (b, h, w) = model._low_rows(cx, ce)
         if buf is None:
             shape = (B, h, w)
             buf = torch.empty(len(wins) * B * h * w, rows.shape[1], device=rows.device, dtype=rows.dtype)
@@ -154,7 +165,7 @@ def _slide_low_rows(model, x, e, crop_size, strides, crop_batch):
 
 @torch.no_grad()
 def msf_scores(model, rgb, modal_x, num_classes, scales, flip, out_shape=None, crop_size=None, stride_rate=None,
-               crop_batch=None):
+               crop_batch=None, slide=None):
     """Summed softmax scores over scales (and flips) of one batch: float32 [B*H*W, ncls] rows
     (val_mm.py:355-392 for one batch; `scaled_logits` of the reference, channels last). Like the
     reference (val_mm.py:355-356) the scaled sizes and the score buffer follow the LABEL's
@@ -162,72 +173,43 @@ def msf_scores(model, rgb, modal_x, num_classes, scales, flip, out_shape=None, c
 
     With crop_size = (hc, wc) every scale runs the reference's sliding-window inference: windows of
     crop_size at a stride of int(stride_rate * crop), at most crop_batch images (default: one window
-    of the batch) per model call."""
+    of the batch) per model call. slide is the same as a validated record (evaluate_msf's)."""
     B, H, W = out_shape if out_shape is not None else (rgb.shape[0], rgb.shape[2], rgb.shape[3])
     if rgb.shape[0] != B or modal_x.shape[0] != B:
         raise ValueError(f"msf_scores: batch of the images {rgb.shape[0]} != labels {B}")
     if crop_size is not None:
-        crop_size = tuple(int(c) for c in crop_size)
-        strides = slide_strides(crop_size, stride_rate)
+        slide = _slide_config(None, crop_size, stride_rate, crop_batch)
     acc = torch.zeros(B * H * W, num_classes, device=rgb.device, dtype=torch.float32)
     for scale in scales:
         size = msf_size(H, W, scale)
         for f in ((False, True) if flip else (False,)):
             x = K.resize_nchw(rgb, size, True, flip=f)
             e = K.resize_nchw(modal_x, size, True, flip=f)
-            if crop_size is not None:
-                rows, (b, h, w), scaled = _slide_low_rows(model, x, e, crop_size, strides, crop_batch)
-                K.slide_msf_accumulate(rows, b, h, w, num_classes, crop_size, strides, scaled, (H, W), f, acc)
+            if slide is not None:
+                rows, (b, h, w), scaled = _slide_low_rows(model, x, e, slide)
+                K.slide_msf_accumulate(rows, b, h, w, num_classes, slide.crop, slide.strides, scaled, (H, W), f, acc)
                 continue
-            low = model._low_logits(x, e)
-            rows, (b, h, w) = _nhwc_rows(low)
+            rows, (b, h, w) = model._low_rows(x, e)
             K.msf_accumulate(rows, b, h, w, num_classes, size, (H, W), f, acc)
     return acc
+
+
+def _slide_rows(model, imgs, modal_xs, ncls, slide):
+    """slide_inference as NHWC rows: (float32 [B*Hs'*Ws', ncls], (B, Hs', Ws'))."""
+    rows, (b, h, w), (Hs, Ws) = _slide_low_rows(model, imgs, modal_xs, slide)
+    out = torch.empty(b * Hs * Ws, ncls, device=rows.device, dtype=torch.float32)
+    K.slide_msf_accumulate(rows, b, h, w, ncls, slide.crop, slide.strides, (Hs, Ws), (Hs, Ws), False, out,
+                           softmax=False)
+    return out, (b, Hs, Ws)
 
 
 @torch.no_grad()
 def slide_inference(model, imgs, modal_xs, config, crop_batch=None):
     """val_mm.py:257-322: the window-averaged logits of imgs, float32 [B, ncls, Hs', Ws'] (an NCHW
     view of NHWC rows), (Hs', Ws') the image size after the reference's up-sizing to the crop."""
-    crop_size = tuple(int(c) for c in config.eval_crop_size)
-    strides = slide_strides(crop_size, config.eval_stride_rate)
-    ncls = config.num_classes
-    rows, (b, h, w), (Hs, Ws) = _slide_low_rows(model, imgs, modal_xs, crop_size, strides, crop_batch)
-    out = torch.empty(b * Hs * Ws, ncls, device=rows.device, dtype=torch.float32)
-    K.slide_msf_accumulate(rows, b, h, w, ncls, crop_size, strides, (Hs, Ws), (Hs, Ws), False, out, softmax=False)
-    return out.view(b, Hs, Ws, ncls).permute(0, 3, 1, 2)
-
-
-@torch.no_grad()
-def evaluate_msf(model, dataloader, config, device, scales, flip, engine=None, save_dir=None, sliding=False):
-    """val_mm.py:325-472. dataloader yields dicts with 'rgb', 'modal_x', 'gt'. Returns the Metrics
-    (a list of every rank's Metrics when engine.distributed, like the reference). sliding=True runs
-    every scale through sliding-window inference with config.eval_crop_size and
-    config.eval_stride_rate (and config.eval_crop_batch images per model call, when set)."""
-    if save_dir is not None:
-        raise NotImplementedError("evaluate_msf: prediction image export is outside the hot path (SURVEY.md §2)")
-    slide = {}
-    if sliding:
-        try:  # optional, and a dict-backed config raises KeyError for a missing name
-            crop_batch = config.eval_crop_batch
-        except (AttributeError, KeyError):
-            crop_batch = None
-        slide = dict(crop_size=tuple(config.eval_crop_size), stride_rate=config.eval_stride_rate,
-                     crop_batch=crop_batch)
-        slide_strides(slide["crop_size"], slide["stride_rate"])  # a bad rate fails before the first batch
-    model.eval()
-    metrics = Metrics(config.num_classes, config.background, device)
-    for batch in dataloader:
-        rgb = batch["rgb"].to(device)
-        modal_x = batch["modal_x"].to(device)
-        gt = batch["gt"].to(device)
-        acc = msf_scores(model, rgb, modal_x, config.num_classes, scales, flip, out_shape=tuple(gt.shape), **slide)
-        metrics.update_rows(acc, gt)
-    if engine is not None and getattr(engine, "distributed", False):
-        all_metrics = [None for _ in range(engine.world_size)]
-        torch.distributed.all_gather_object(all_metrics, metrics)
-        return all_metrics
-    return metrics
+    slide = _slide_config(config)._replace(crop_batch=crop_batch)
+    out, shape = _slide_rows(model, imgs, modal_xs, config.num_classes, slide)
+    return out.view(*shape, -1).permute(0, 3, 1, 2)
 
 
 def pred_png_name(fn):
@@ -255,13 +237,6 @@ def check_palette(palette, num_classes):
     return pal
 
 
-def _optional(config, name):
-    try:  # a dict-backed config raises KeyError for a missing name
-        return getattr(config, name)
-    except (AttributeError, KeyError):
-        return None
-
-
 def _write_pred_png(path, pred, palette):
     try:
         from PIL import Image
@@ -285,31 +260,53 @@ def _batch_inputs(batch, device):
     return rgb.to(device), modal_x.to(device), gt.to(device)
 
 
-def _update_batch(model, metrics, rgb, modal_x, gt, config, sliding, want_pred):
-    """One batch of evaluate / save_preds: the histogram update and, when asked for, the uint8 class map
-    [B, H, W] (on the device)."""
-    ncls = config.num_classes
-    if sliding:
-        scores = slide_inference(model, rgb, modal_x, config, _optional(config, "eval_crop_batch"))
-        if tuple(scores.shape[-2:]) != tuple(gt.shape[-2:]):
-            raise ValueError(f"evaluate: sliding-window predictions {tuple(scores.shape[-2:])} do not match the "
-                             f"labels {tuple(gt.shape[-2:])}")
-        rows = scores.permute(0, 2, 3, 1).reshape(-1, ncls)  # the NHWC rows behind slide_inference's view
-        metrics.update_rows(rows, gt)
-        return K.rows_argmax(rows, ncls).view(gt.shape) if want_pred else None
-    if tuple(gt.shape[-2:]) != tuple(rgb.shape[-2:]):
-        raise ValueError(f"evaluate: labels {tuple(gt.shape[-2:])} do not match the image {tuple(rgb.shape[-2:])}")
-    rows, shape = _nhwc_rows(model._low_logits(rgb, modal_x))
-    pred = torch.empty(gt.shape, device=rows.device, dtype=torch.uint8) if want_pred else None
-    return metrics.update_low(rows, shape, gt, pred=pred)
-
-
-def _gathered(metrics, engine):
+def _run(model, dataloader, config, device, engine, sliding, step):
+    """The loop of evaluate_msf, evaluate and save_preds: step(metrics, slide, batch, rgb, modal_x, gt) per
+    batch, slide being config's sliding-window settings (None unless sliding). Returns the Metrics (a list
+    of every rank's Metrics when engine.distributed, like the reference)."""
+    slide = _slide_config(config) if sliding else None  # a bad rate fails before the first batch
+    model.eval()
+    metrics = Metrics(config.num_classes, config.background, device)
+    for batch in dataloader:
+        step(metrics, slide, batch, *_batch_inputs(batch, device))
     if engine is not None and getattr(engine, "distributed", False):
         all_metrics = [None for _ in range(engine.world_size)]
         torch.distributed.all_gather_object(all_metrics, metrics)
         return all_metrics
     return metrics
+
+
+@torch.no_grad()
+def evaluate_msf(model, dataloader, config, device, scales, flip, engine=None, save_dir=None, sliding=False):
+    """val_mm.py:325-472. dataloader yields dicts with 'rgb', 'modal_x' (or 'laser'), 'gt'. Returns the
+    Metrics (a list of every rank's Metrics when engine.distributed, like the reference). sliding=True
+    runs every scale through sliding-window inference with config.eval_crop_size and
+    config.eval_stride_rate (and config.eval_crop_batch images per model call, when set)."""
+    if save_dir is not None:
+        raise NotImplementedError("evaluate_msf: prediction image export is outside the hot path (SURVEY.md §2)")
+
+    def step(metrics, slide, batch, rgb, modal_x, gt):
+        acc = msf_scores(model, rgb, modal_x, config.num_classes, scales, flip, out_shape=tuple(gt.shape), slide=slide)
+        metrics.update_rows(acc, gt)
+
+    return _run(model, dataloader, config, device, engine, sliding, step)
+
+
+def _update_batch(model, metrics, slide, rgb, modal_x, gt, want_pred):
+    """One batch of evaluate / save_preds: the histogram update and, when asked for, the uint8 class map
+    [B, H, W] (on the device)."""
+    if slide is not None:
+        rows, shape = _slide_rows(model, rgb, modal_x, metrics.num_classes, slide)
+        if shape[1:] != tuple(gt.shape[-2:]):
+            raise ValueError(f"evaluate: sliding-window predictions {shape[1:]} do not match the labels "
+                             f"{tuple(gt.shape[-2:])}")
+        metrics.update_rows(rows, gt)
+        return K.rows_argmax(rows, metrics.num_classes).view(gt.shape) if want_pred else None
+    if tuple(gt.shape[-2:]) != tuple(rgb.shape[-2:]):
+        raise ValueError(f"evaluate: labels {tuple(gt.shape[-2:])} do not match the image {tuple(rgb.shape[-2:])}")
+    rows, shape = model._low_rows(rgb, modal_x)
+    pred = torch.empty(gt.shape, device=rows.device, dtype=torch.uint8) if want_pred else None
+    return metrics.update_low(rows, shape, gt, pred=pred)
 
 
 @torch.no_grad()
@@ -319,22 +316,19 @@ def evaluate(model, dataloader, config, device, engine=None, save_dir=None, slid
     save_dir writes <save_dir>/<name>_pred.png for every image of a batch: coloured with `palette`
     (else config.palette; uint8 [>= num_classes, 3], the caller's data) or, without one, the class
     indices as an 8-bit image."""
-    if sliding:
-        slide_strides(tuple(config.eval_crop_size), config.eval_stride_rate)  # a bad rate fails before the first batch
     if save_dir is not None:
         if palette is None:
             palette = _optional(config, "palette")
         if palette is not None:
             palette = check_palette(palette, config.num_classes)
-    model.eval()
-    metrics = Metrics(config.num_classes, config.background, device)
-    for batch in dataloader:
-        rgb, modal_x, gt = _batch_inputs(batch, device)
-        pred = _update_batch(model, metrics, rgb, modal_x, gt, config, sliding, save_dir is not None)
+
+    def step(metrics, slide, batch, rgb, modal_x, gt):
+        pred = _update_batch(model, metrics, slide, rgb, modal_x, gt, save_dir is not None)
         if save_dir is not None:
             for p, fn in zip(pred.cpu().numpy(), batch["fn"]):
                 _write_pred_png(os.path.join(save_dir, pred_png_name(fn) + "_pred.png"), p, palette)
-    return _gathered(metrics, engine)
+
+    return _run(model, dataloader, config, device, engine, sliding, step)
 
 
 @torch.no_grad()
@@ -342,15 +336,12 @@ def save_preds(model, dataloader, config, device, engine=None, model_path=None, 
     """val_mm.py:25-98: the metrics of `evaluate` plus one <out_root>/<model_path>/<img_id>.npy uint8 class
     map per image, img_id from batch['rgb_path'][i] (pred_img_id)."""
     import numpy as np
-    if sliding:
-        slide_strides(tuple(config.eval_crop_size), config.eval_stride_rate)
     out_dir = os.path.join(out_root, str(model_path))
-    os.makedirs(out_dir, exist_ok=True)
-    model.eval()
-    metrics = Metrics(config.num_classes, config.background, device)
-    for batch in dataloader:
-        rgb, modal_x, gt = _batch_inputs(batch, device)
-        pred = _update_batch(model, metrics, rgb, modal_x, gt, config, sliding, True)
+
+    def step(metrics, slide, batch, rgb, modal_x, gt):
+        pred = _update_batch(model, metrics, slide, rgb, modal_x, gt, True)
+        os.makedirs(out_dir, exist_ok=True)
         for p, path in zip(pred.cpu().numpy(), batch["rgb_path"]):
             np.save(os.path.join(out_dir, pred_img_id(path) + ".npy"), p)
-    return _gathered(metrics, engine)
+
+    return _run(model, dataloader, config, device, engine, sliding, step)

@@ -75,6 +75,10 @@ class EncoderDecoder(nn.Module):
         K.TAG = "decoder"
         return self.decode_head.forward(outs)
 
+    def _low_rows(self, rgb, modal_x):
+        """The low-res logits as NHWC rows: ([B*h*w, ncls], (B, h, w))."""
+        return _nhwc_rows(self._low_logits(rgb, modal_x))
+
     def _upsample(self, low, size):
         rows, (B, h, w) = _nhwc_rows(low)
         up = K.bilinear(rows.contiguous(), (h, w), tuple(size), B)
@@ -88,7 +92,7 @@ class EncoderDecoder(nn.Module):
     def predict(self, rgb, modal_x):
         """The class map of the eval forward, uint8 [B, H, W]: forward(rgb, modal_x).argmax(1) without the
         full-resolution logits (one fused upsample + argmax kernel over the low-res logits)."""
-        rows, (B, h, w) = _nhwc_rows(self._low_logits(rgb, modal_x))
+        rows, (B, h, w) = self._low_rows(rgb, modal_x)
         K.TAG = "eval"
         return K.seg_predict(rows, B, h, w, rows.shape[1], tuple(rgb.shape[-2:]))
 

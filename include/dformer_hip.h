@@ -420,9 +420,11 @@ int dfm_conv3_weight_unpack(int Cout, int Cin, int Kp, const float* dwp, float* 
  * msf_accumulate: acc [B*H*W][ncls] float32 (NHWC rows) += softmax over classes of the decoder's
  *   low-res logits low [B*h*w][ldl] upsampled to (Hs, Ws) with align_corners=False (the model's
  *   output at scale s, builder.py:203), flipped back along W when flip, then resized to (H, W)
- *   with align_corners=True. ncls <= 64.
+ *   with align_corners=True. ncls <= 64. Runs slide_msf_accumulate's kernel with one window that covers
+ *   the scaled image (crop = stride = (Hs, Ws), softmax).
  * seg_confusion: hist [ncls*ncls] uint64 += bincount(label * ncls + argmax(acc)) over pixels
- *   whose label != ignore (and within [0, ncls)). */
+ *   whose label != ignore (and within [0, ncls)); the argmax is rows_argmax's (one kernel: the first
+ *   maximum of the float32 row), counted instead of stored. */
 int dfm_resize_nchw(int dtype_in, int dtype_out, int B, int C, int Hi, int Wi, long sb, long sc, long sh, long sw,
                     const void* x, int Ho, int Wo, int align_corners, int flip, void* y, dfm_stream_t stream);
 int dfm_msf_accumulate(int dtype, int B, int h, int w, int ncls, const void* low, long ldl, int Hs, int Ws, int H,

@@ -1,5 +1,7 @@
 """Multi-scale + flip evaluation (dformer_amd.evaluate, csrc/eval.hip) against torch / the oracle's
 restatement of utils/val_mm.py:355-392 and utils/metrics_new.py:16-47."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -39,13 +41,24 @@ def test_resize_nchw(align, flip, src, dst):
 
 
 @pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("ncls", [40, 37, 13, 64])
+@pytest.mark.parametrize("ncls", [40, 37, 13, 64, 1, 9])  # 1: lanes without a class; 9: one lane's second round
 @pytest.mark.parametrize("flip", [False, True])
 def test_msf_accumulate(dt, ncls, flip):
+    run_msf_accumulate(dt, ncls, flip, (2, 9, 12, 72, 96, 61, 83))
+
+
+@pytest.mark.parametrize("flip", [False, True])
+def test_msf_accumulate_identity(flip):
+    """(Hs, Ws) == (H, W): the align_corners=True resize is the identity."""
+    run_msf_accumulate(torch.float32, 40, flip, (1, 3, 4, 24, 32, 24, 32))
+
+
+def run_msf_accumulate(dt, ncls, flip, geom):
     from dformer_amd import kernels as K
-    B, h, w, Hs, Ws, H, W = 2, 9, 12, 72, 96, 61, 83
+    B, h, w, Hs, Ws, H, W = geom
     low = torch.randn(B, ncls, h, w, device=DEV).to(dt)
-    rows = low.permute(0, 2, 3, 1).contiguous().view(-1, ncls)
+    # a fresh buffer: with one class, contiguous() keeps the permuted view and its class stride of h * w
+    rows = torch.empty(B * h * w, ncls, device=DEV, dtype=dt).copy_(low.permute(0, 2, 3, 1).reshape(-1, ncls))
     acc0 = torch.rand(B * H * W, ncls, device=DEV)
     acc = K.msf_accumulate(rows, B, h, w, ncls, (Hs, Ws), (H, W), flip, acc0.clone())
     lg = F.interpolate(low.float(), size=(Hs, Ws), mode="bilinear", align_corners=False)
@@ -56,19 +69,53 @@ def test_msf_accumulate(dt, ncls, flip):
     assert rel(acc.view(B, H, W, ncls), ref) < 1e-5
 
 
-def test_confusion_matches_bincount():
+@functools.lru_cache(maxsize=None)
+def confusion_case(ncls):
+    """(scores [3*50*70, ncls] with the tie patterns of test_predict_gpu.py's test_rows_argmax, labels
+    [3, 50, 70] with ignored and out-of-range ones, the labels to count). 10500 rows are no multiple of the
+    32 rows a workgroup takes at a time."""
+    g = torch.Generator(device="cpu").manual_seed(3)
+    acc = torch.rand(3 * 50 * 70, ncls, generator=g)
+    acc[:40] = 0.5                       # whole rows tied: the first maximum wins, like torch.argmax
+    if ncls > 5:
+        acc[40:80, 5] = 9.0              # ties between two lanes of a group, and within one lane
+        acc[40:80, ncls - 1] = 9.0
+        acc[80:120, 3] = 9.0
+        acc[80:120, min(11, ncls - 1)] = 9.0
+    lab = torch.randint(0, ncls, (3, 50, 70), generator=g)
+    lab[torch.rand(3, 50, 70, generator=g) < 0.1] = 255
+    lab.view(-1)[100:104] = torch.tensor([-1, ncls, 300, -7])  # out of range: skipped
+    keep = (lab != 255) & (lab >= 0) & (lab < ncls)
+    assert 0 < int(keep.sum()) < keep.numel() - 4
+    return acc.to(DEV), lab.to(DEV), keep.to(DEV)
+
+
+@pytest.mark.parametrize("ncls", [1, 7, 40, 64])
+def test_confusion_matches_bincount(ncls):
     from dformer_amd import kernels as K
-    ncls = 40
-    acc = torch.rand(3 * 50 * 70, ncls, device=DEV)
-    acc[:5] = 0.5  # ties: the first maximum wins, like torch.argmax
-    lab = torch.randint(0, ncls, (3, 50, 70), device=DEV)
-    lab[torch.rand(3, 50, 70, device=DEV) < 0.1] = 255
+    acc, lab, keep = confusion_case(ncls)
     hist = torch.zeros(ncls * ncls, dtype=torch.int64, device=DEV)
     K.seg_confusion(acc, lab, ncls, 255, hist)
+    ref = torch.bincount(lab[keep] * ncls + acc.argmax(1).view(lab.shape)[keep], minlength=ncls * ncls)
+    assert int(ref.sum()) == int(keep.sum())
+    assert torch.equal(hist, ref)
     K.seg_confusion(acc, lab, ncls, 255, hist)  # accumulates
+    assert torch.equal(hist, 2 * ref)
+    # the oracle's Metrics.update, which knows no label outside [0, ncls) but the ignored one
     scores = acc.view(3, 50, 70, ncls).permute(0, 3, 1, 2)
-    ref = R.confusion(scores.cpu(), lab.cpu(), ncls)
-    assert torch.equal(hist.cpu().view(ncls, ncls), 2 * ref)
+    inside = torch.where(keep, lab, torch.full_like(lab, 255))
+    assert torch.equal(hist.cpu().view(ncls, ncls), 2 * R.confusion(scores.cpu(), inside.cpu(), ncls))
+
+
+@pytest.mark.parametrize("ncls", [1, 7, 40, 64])
+def test_confusion_counts_the_rows_argmax(ncls):
+    """dfm_seg_confusion and dfm_rows_argmax are one kernel: the histogram is the bincount of the stored argmax."""
+    from dformer_amd import kernels as K
+    acc, lab, keep = confusion_case(ncls)
+    hist = torch.zeros(ncls * ncls, dtype=torch.int64, device=DEV)
+    K.seg_confusion(acc, lab, ncls, 255, hist)
+    pred = K.rows_argmax(acc, ncls).view(lab.shape)
+    assert torch.equal(hist, torch.bincount(lab[keep] * ncls + pred[keep].long(), minlength=ncls * ncls))
 
 
 class Cfg(dict):

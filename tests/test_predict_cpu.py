@@ -144,6 +144,32 @@ def test_gt_size_mismatch_raises_before_the_model():
                  sliding=True)
 
 
+def test_bad_stride_rate_raises_before_the_first_batch(tmp_path):
+    """sliding=True with a stride of int(0 * crop) = 0: every entry point raises before it iterates."""
+    from dformer_amd.evaluate import evaluate, evaluate_msf, save_preds
+
+    class Cfg(dict):
+        __getattr__ = dict.__getitem__
+
+    class Model:
+        def eval(self):
+            return self
+
+    class Loader:
+        def __iter__(self):
+            raise AssertionError("the dataloader was touched")
+
+    cfg = Cfg(num_classes=4, background=255, eval_crop_size=[32, 32], eval_stride_rate=0.0)
+    with pytest.raises(ValueError, match="must be positive"):
+        evaluate_msf(Model(), Loader(), cfg, "cpu", [1.0], False, sliding=True)
+    with pytest.raises(ValueError, match="must be positive"):
+        evaluate(Model(), Loader(), cfg, "cpu", sliding=True)
+    with pytest.raises(ValueError, match="must be positive"):
+        save_preds(Model(), Loader(), cfg, "cpu", model_path="run", sliding=True, out_root=str(tmp_path))
+    with pytest.raises(AssertionError, match="touched"):  # a good rate gets as far as the loader
+        evaluate(Model(), Loader(), Cfg(cfg, eval_stride_rate=0.5), "cpu", sliding=True)
+
+
 @pytest.mark.parametrize("name,ncls", [("eval_tiny_ham", 40), ("eval_tiny_mlp", 37)])
 def test_fixture_is_self_consistent(name, ncls):
     """hist of the reference's evaluate == bincount over its own argmax maps and gen's labels."""

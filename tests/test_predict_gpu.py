@@ -290,6 +290,30 @@ def test_save_preds_writes_one_map_per_image(ham64, tmp_path, sliding):
             assert got.dtype == np.uint8 and np.array_equal(got, pred[j])
 
 
+def test_distributed_engine_returns_every_ranks_metrics(ham64, tmp_path, monkeypatch):
+    """engine.distributed: a list with one Metrics per rank (here one), equal to the call without an engine."""
+    from types import SimpleNamespace
+    from dformer_amd.evaluate import Metrics, evaluate, evaluate_msf, save_preds
+    model, cfg, loader = ham64
+    gathered = []
+
+    def all_gather_object(out, obj):
+        out[0] = obj
+        gathered.append(obj)
+
+    monkeypatch.setattr(torch.distributed, "all_gather_object", all_gather_object)
+    runs = {"evaluate_msf": lambda e: evaluate_msf(model, loader, cfg, DEV, [1.0], False, engine=e),
+            "evaluate": lambda e: evaluate(model, loader, cfg, DEV, engine=e),
+            "save_preds": lambda e: save_preds(model, loader, cfg, DEV, engine=e, model_path="run",
+                                               out_root=str(tmp_path))}
+    for name, run in runs.items():
+        got = run(SimpleNamespace(distributed=True, world_size=1))
+        assert isinstance(got, list) and len(got) == 1 and isinstance(got[0], Metrics), name
+        assert got[0] is gathered[-1]
+        assert torch.equal(got[0]._hist, run(None)._hist) and int(got[0]._hist.sum()) > 0, name
+    assert len(gathered) == 3
+
+
 def test_evaluate_save_dir_writes_pngs(ham64, tmp_path):
     Image = pytest.importorskip("PIL.Image")
     from dformer_amd.evaluate import evaluate

@@ -9,8 +9,9 @@ GPU being idle when the first event is recorded):
   fused       Metrics.update_low (K.seg_predict, histogram only)
   fused+pred  the same, also writing the uint8 class map
   upsample    EncoderDecoder._upsample (K.bilinear to [B, ncls, H, W]) + Metrics.update
-  msf         K.msf_accumulate into a zeroed [B*H*W, ncls] buffer + Metrics.update_rows
-              (what evaluate_msf(scales=[1], flip=False) does per batch)
+  msf         K.msf_accumulate (the sliding-window accumulate kernel on one window) into a zeroed
+              [B*H*W, ncls] buffer + Metrics.update_rows (the rows_argmax kernel with a label): what
+              evaluate_msf(scales=[1], flip=False) does per batch
 and reports the dfm_seg_predict kernel alone (the library's launch tracer), the achieved bytes/s against the algorithmic bytes of DESIGN.md §3 (ncls * es per low-res pixel
 + 8 B label [+ 1 B prediction] per output pixel) and the peak memory each path allocates.
 """

@@ -65,7 +65,8 @@ def worker(dtype, reps, crop_batch):
     dep = torch.randn(B, 1, H, W, device=dev, generator=g)
     gt = torch.randint(0, NCLS, (B, H, W), device=dev, generator=g)
     loader = [{"rgb": rgb, "modal_x": dep, "gt": gt}]
-    strides = E.slide_strides(CROP, RATE)
+    slide = E._slide_config(cfg)  # crop, strides and cfg's crops per model call
+    strides = slide.strides
     combos = [(s, f) for s in SCALES for f in (False, True)]
 
     def inputs(scale, flip):
@@ -99,7 +100,7 @@ def worker(dtype, reps, crop_batch):
         scores = torch.zeros(B, NCLS, H, W, device=dev)
         for scale, flip in combos:
             x, e = inputs(scale, flip)
-            rows, (b, h, w), scaled = E._slide_low_rows(model, x, e, CROP, strides, crop_batch or None)
+            rows, (b, h, w), scaled = E._slide_low_rows(model, x, e, slide)
             torch_tail(rows, b, h, w, scaled, flip, scores)
         metrics.update(scores, gt)
         return metrics
@@ -108,7 +109,7 @@ def worker(dtype, reps, crop_batch):
         lows = []
         for scale, flip in combos:
             x, e = inputs(scale, flip)
-            lows.append(E._slide_low_rows(model, x, e, CROP, strides, crop_batch or None) + (flip,))
+            lows.append(E._slide_low_rows(model, x, e, slide) + (flip,))
     acc = torch.zeros(B * H * W, NCLS, device=dev)
     scores = torch.zeros(B, NCLS, H, W, device=dev)
 
