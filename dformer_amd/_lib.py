@@ -148,6 +148,8 @@ _SIGS = {
                                    c_long, c_int, P]),
     "dfm_conv3s2_col2im_nchw": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, c_long,
                                         c_long, c_long, P]),
+    "dfm_conv3s1_im2col": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P]),
+    "dfm_conv3s1_col2im": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, c_int, P]),
     "dfm_conv3_weight_pack": (c_int, [c_int, c_int, c_int, c_int, P, P, P]),
     "dfm_conv3_weight_unpack": (c_int, [c_int, c_int, c_int, P, P, c_int, P]),
     "dfm_resize_nchw": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long, P, c_int,

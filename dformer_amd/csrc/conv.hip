@@ -12,6 +12,8 @@
 // Backward: dcols = dy @ Wp (dfm_gemm), then dfm_conv3s2_col2im gathers the <= 4 taps that touch
 // every input pixel in a fixed order (deterministic, no atomics) and applies the recomputed GELU'
 // of the folded BN output; the BN backward itself runs on the library's BN kernels.
+// The auxiliary FCN head's stride-1 conv (fcnhead.py:19) uses the same column order and packed weight
+// with a gather / col2im pair of its own (dfm_conv3s1_*), without the folded BN.
 #include "common.h"
 
 namespace {
@@ -206,6 +208,79 @@ __global__ __launch_bounds__(kThreads) void col2im_gen_kernel(int B, int Cin, in
   }
 }
 
+// ---- dense 3x3 stride-1 pad-1 conv of the auxiliary FCN head (fcnhead.py:19) on NHWC rows: the same
+// (kh, kw, c) column order, no folded BN / GELU (the input is a Block output), Cin % 8 == 0.
+// One thread = one pixel p, one tap, 8 consecutive channels; Kp == 9*Cin (no pad columns).
+template <typename T, typename I>
+__global__ __launch_bounds__(kThreads) void im2col_s1_kernel(int B, int H, int W, int Cin, const T* __restrict__ x,
+                                                             long ldx, T* __restrict__ cols, long ldc) {
+  const I cv = (I)(Cin >> 3);
+  const I n = (I)((long)B * H * W * 9 * cv);
+  for (I i = blockIdx.x * (I)blockDim.x + threadIdx.x; i < n; i += (I)gridDim.x * blockDim.x) {
+    const int c0 = (int)(i % cv) * 8;
+    const I rest = i / cv;
+    const int tap = (int)(rest % 9u);
+    const I pi = rest / 9u;
+    const int ow = (int)(pi % (I)W);
+    const I t = pi / (I)W;
+    const int oh = (int)(t % (I)H);
+    const long b = (long)(t / (I)H);
+    const int ih = oh - 1 + tap / 3, iw = ow - 1 + tap % 3;
+    float v[8];
+    if (ih >= 0 && ih < H && iw >= 0 && iw < W) {
+      ld8<T>(x + ((b * H + ih) * W + iw) * ldx + c0, v);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = 0.f;
+    }
+    st8<T>(cols + (long)pi * ldc + tap * Cin + c0, v);
+  }
+}
+
+// dx[(b, ih, iw), c..c+7] (+)= sum over the taps (kh, kw) with oh = ih+1-kh, ow = iw+1-kw inside the
+// image of dcols[(b, oh, ow), (kh*3+kw)*Cin + c..]; taps visited in a fixed order, one owner per element.
+template <typename T, typename I>
+__global__ __launch_bounds__(kThreads) void col2im_s1_kernel(int B, int H, int W, int Cin,
+                                                             const T* __restrict__ dcols, long ldc,
+                                                             T* __restrict__ dx, long lddx, int accumulate) {
+  const I cv = (I)(Cin >> 3);
+  const I n = (I)((long)B * H * W * cv);
+  for (I i = blockIdx.x * (I)blockDim.x + threadIdx.x; i < n; i += (I)gridDim.x * blockDim.x) {
+    const int c0 = (int)(i % cv) * 8;
+    const long p = (long)(i / cv);
+    const I pi = i / cv;
+    const int iw = (int)(pi % (I)W);
+    const I t = pi / (I)W;
+    const int ih = (int)(t % (I)H);
+    const long b = (long)(t / (I)H);
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+      const int oh = ih + 1 - kh;
+      if (oh < 0 || oh >= H) continue;
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) {
+        const int ow = iw + 1 - kw;
+        if (ow < 0 || ow >= W) continue;
+        float v[8];
+        ld8<T>(dcols + ((b * H + oh) * W + ow) * ldc + (kh * 3 + kw) * Cin + c0, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += v[e];
+      }
+    }
+    T* dp = dx + p * lddx + c0;
+    if (accumulate) {
+      float o[8];
+      ld8<T>(dp, o);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] += o[e];
+    }
+    st8<T>(dp, acc);
+  }
+}
+
 // w float32 [Cout][Cin][3][3] -> wp [Cout][Kp], wp[o][(kh*3+kw)*Cin + c] (zero past 9*Cin)
 template <typename To>
 __global__ void weight_pack_kernel(int Cout, int Cin, int Kp, const float* __restrict__ w, To* __restrict__ wp) {
@@ -356,6 +431,54 @@ extern "C" int dfm_conv3s2_col2im_nchw(int dtype, int dtype_out, int B, int H, i
     return DFM_ERR_DTYPE;
   }
 #undef DFM_C2I
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+extern "C" int dfm_conv3s1_im2col(int dtype, int B, int H, int W, int Cin, const void* x, long ldx, void* cols,
+                                  long ldc, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  DFM_CHECK_ARG(x && cols, "dfm_conv3s1_im2col: null argument");
+  DFM_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0, "dfm_conv3s1_im2col: bad shape");
+  DFM_CHECK_ARG(Cin % 8 == 0, "dfm_conv3s1_im2col: Cin=%d must be a multiple of 8", Cin);
+  DFM_CHECK_ARG(ldx >= Cin && ldx % 8 == 0 && ldc >= 9L * Cin && ldc % 8 == 0,
+                "dfm_conv3s1_im2col: row strides must be multiples of 8 covering Cin / 9*Cin");
+  DFM_CHECK_ARG((uintptr_t)x % 16 == 0 && (uintptr_t)cols % 16 == 0,
+                "dfm_conv3s1_im2col: operands must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const long n = (long)B * H * W * 9 * (Cin / 8);
+#define DFM_I2C1(T, I)                                                                                    \
+  DFM_LAUNCH((im2col_s1_kernel<T, I>), dim3(grid_for(n)), dim3(kThreads), 0, s, B, H, W, Cin, (const T*)x, \
+             ldx, (T*)cols, ldc)
+  const bool i32 = n < (1L << 31);
+  DFM_DTYPE_SWITCH(dtype, T, {
+    if (i32) DFM_I2C1(T, unsigned); else DFM_I2C1(T, long);
+  });
+#undef DFM_I2C1
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+extern "C" int dfm_conv3s1_col2im(int dtype, int B, int H, int W, int Cin, const void* dcols, long ldc, void* dx,
+                                  long lddx, int accumulate, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  DFM_CHECK_ARG(dcols && dx, "dfm_conv3s1_col2im: null argument");
+  DFM_CHECK_ARG(B > 0 && H > 0 && W > 0 && Cin > 0, "dfm_conv3s1_col2im: bad shape");
+  DFM_CHECK_ARG(Cin % 8 == 0, "dfm_conv3s1_col2im: Cin=%d must be a multiple of 8", Cin);
+  DFM_CHECK_ARG(ldc >= 9L * Cin && ldc % 8 == 0 && lddx >= Cin && lddx % 8 == 0,
+                "dfm_conv3s1_col2im: row strides must be multiples of 8 covering 9*Cin / Cin");
+  DFM_CHECK_ARG((uintptr_t)dcols % 16 == 0 && (uintptr_t)dx % 16 == 0,
+                "dfm_conv3s1_col2im: operands must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const long n = (long)B * H * W * (Cin / 8);
+#define DFM_C2I1(T, I)                                                                                         \
+  DFM_LAUNCH((col2im_s1_kernel<T, I>), dim3(grid_for(n)), dim3(kThreads), 0, s, B, H, W, Cin, (const T*)dcols, \
+             ldc, (T*)dx, lddx, accumulate)
+  const bool i32 = n < (1L << 31);
+  DFM_DTYPE_SWITCH(dtype, T, {
+    if (i32) DFM_C2I1(T, unsigned); else DFM_C2I1(T, long);
+  });
+#undef DFM_C2I1
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }

@@ -2,6 +2,7 @@
 
   LightHamHead (+ Hamburger, NMF2D)   models/decoders/ham_head.py:11-240, decode_head.py:55-231
   DecoderHead (MLPDecoder)            models/decoders/MLPDecoder.py:8-81
+  FCNHead (auxiliary head)            models/decoders/fcnhead.py:9-29, builder.py:138-143
   seg_loss                            models/builder.py:203,230
 
 Feature maps are NHWC rows [B*h*w, C] in the compute dtype. BatchNorm runs in training mode on
@@ -149,11 +150,12 @@ class LinearActFn(torch.autograd.Function):
         K.linear(x, Wc, b, act=act, out=out)
         ctx.save_for_backward(x, w, b, out)
         ctx.act = act
+        ctx.tag = "aux.bwd" if K.TAG == "aux" else "decoder.bwd"
         return out
 
     @staticmethod
     def backward(ctx, dy):
-        K.TAG = "decoder.bwd"
+        K.TAG = ctx.tag
         x, w, b, y = ctx.saved_tensors
         dy = dy.contiguous()
         if ctx.act == 2:
@@ -564,6 +566,11 @@ class LightHamHead(nn.Module):
     """LightHamHead (ham_head.py:184-240) + BaseDecodeHead pieces (decode_head.py:55-231).
     forward(list of 4 NCHW maps) -> logits NCHW view of NHWC rows [B, ncls, H/8, W/8]."""
 
+    # The reference's BaseDecodeHead registers conv_seg before the head's own modules (decode_head.py:104),
+    # this class after them. train.group_weight walks children in this order, so the optimizer's parameter
+    # indices are the reference's; parameters() / state_dict() order (and a seeded init) stay as they are.
+    reference_children = ("conv_seg", "squeeze", "hamburger", "align")
+
     def __init__(self, ham_channels=512, ham_kwargs=None, in_channels=(128, 256, 512), channels=512, num_classes=40,
                  dropout_ratio=0.1, norm_cfg=None, in_index=(1, 2, 3), align_corners=False, bn_eps=1e-3,
                  bn_momentum=0.1, device=None, **kwargs):
@@ -763,6 +770,79 @@ class MLPFoldFn(torch.autograd.Function):
         for i in range(4):
             grads += [drows[i], dLs[i].view_as(Ls[i]), dbs[i]]
         return (None, None, None, None, None, dWf.view_as(wf), dbf, dgamma, dbeta, *grads)
+
+
+# ============================================================================= auxiliary FCN head
+class Conv3BNReLUFn(torch.autograd.Function):
+    """y = relu(BN(conv3x3(x) + b)) — FCNHead.conv (fcnhead.py:18-22): nn.Conv2d(cin, cout, 3, padding=1),
+    BatchNorm / SyncBatchNorm, ReLU on NHWC rows. The conv is ONE gather (csrc/conv.hip, stride 1) and ONE
+    MFMA GEMM over the packed weight with the bias in its epilogue, like the stems' ConvS2Fn. Backward:
+    ReLU' and the BN backward, weight / bias gradients from the saved gathered operand, input gradient by
+    the transposed GEMM + the deterministic col2im."""
+
+    @staticmethod
+    def forward(ctx, x, shape, w, b, gamma, beta, bn, sync):
+        dt = x.dtype
+        cin = x.shape[1]
+        cols = K.conv3s1_im2col(x, shape)
+        wp = K.conv3_weight_pack(w.detach(), dt, K.conv3s2_kp(cin))
+        y0 = K.linear(cols, wp, b.detach())
+        count = y0.shape[0]
+        if bn.training:
+            mean, rstd, count = bn_batch_stats(y0, bn, sync)
+        else:
+            mean, rstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
+        y = K.bn_apply(y0, mean, rstd, gamma, beta, act=2)
+        ctx.save_for_backward(cols, wp, w, b, y0, y, mean, rstd, gamma)
+        ctx.meta = (shape, cin, count, sync, bn, bn.training)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        K.TAG = "aux.bwd"
+        cols, wp, w, b, y0, y, mean, rstd, gamma = ctx.saved_tensors
+        shape, cin, count, sync, bn, training = ctx.meta
+        dy = K.relu_bwd(dy.contiguous(), y)
+        st2, dgamma, dbeta = bn_grad_stats(y0, dy, mean, rstd, bn, sync)
+        if training:
+            dy0 = K.bn_bwd_apply(y0, dy, mean, rstd, gamma, st2, count)
+        else:  # running statistics: BN is a fixed per-channel affine
+            dy0 = K.scale_mul(dy, colscale=rstd * gamma)
+        dwp, db = K.linear_wgrad(dy0, cols, bias_grad=True, bias_out=gslot(b))
+        dw = K.conv3_weight_unpack(dwp, cin, dw=gslot(w))
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.conv3s1_col2im(K.linear_dgrad(dy0, wp), shape, cin)
+        return dx, None, dw, db, dgamma, dbeta, None, None
+
+
+class FCNHead(nn.Module):
+    """FCNHead (fcnhead.py:9-29), the auxiliary head of builder.py:138-143: conv3x3 + BN + ReLU, then a 1x1
+    classifier, with the reference's submodule names. forward(NCHW map) -> logits NCHW view of NHWC rows.
+    `channels` is the hidden width; builder.py:143 passes cfg.num_classes there and leaves `num_classes`
+    at its default of 40, so the head's output is always 40 wide (reproduced by the caller)."""
+
+    def __init__(self, in_channels=384, channels=None, kernel_size=3, dilation=1, num_classes=40,
+                 norm_layer=nn.BatchNorm2d, bn_eps=1e-3, bn_momentum=0.1, syncbn=False):
+        super().__init__()
+        if kernel_size != 3 or dilation != 1:
+            raise NotImplementedError("FCNHead: only the 3x3, dilation-1 conv of builder.py:143 has a kernel")
+        self.kernel_size = kernel_size
+        self.in_channels = in_channels
+        self.channels = channels or in_channels // 4
+        self.num_classes = num_classes
+        self.conv = nn.Sequential(nn.Conv2d(self.in_channels, self.channels, kernel_size, padding=1),
+                                  norm_layer(self.channels, eps=bn_eps, momentum=bn_momentum),
+                                  nn.ReLU(inplace=True))
+        self.classifier = nn.Conv2d(self.channels, num_classes, kernel_size=1)
+        self.syncbn = syncbn or isinstance(self.conv[1], nn.SyncBatchNorm)
+
+    def forward(self, x):
+        rows, (B, H, W) = _nhwc_rows(x)
+        conv, bn = self.conv[0], self.conv[1]
+        y = Conv3BNReLUFn.apply(rows, (B, H, W), conv.weight, conv.bias, bn.weight, bn.bias, bn, self.syncbn)
+        logits = LinearActFn.apply(y, self.classifier.weight, self.classifier.bias, 0, False)
+        return logits.view(B, H, W, self.num_classes).permute(0, 3, 1, 2)
 
 
 # ========================================================================================== loss

@@ -787,7 +787,7 @@ def bn_bwd_apply(x, dy, mean, rstd, gamma, stats2, count, dx=None, accumulate=Fa
     return dx
 
 
-# ------------------------------------------------------------------- dense 3x3 stride-2 conv
+# ------------------------------------------------- dense 3x3 conv (stride 2: stems; stride 1: aux head)
 def conv3s2_kp(cin):
     """Packed K (columns of the gathered operand): 9*cin rounded up to a multiple of 8."""
     return (9 * cin + 7) // 8 * 8
@@ -837,6 +837,33 @@ def conv3s2_col2im_nchw(dcols, shape, cin, dtype):
                                       ptr(dx), sb, sc, sh, sw, stream()), "dfm_conv3s2_col2im_nchw")
     if ACCOUNT is not None:
         _acct(0, dcols.shape[0] * 9 * cin * _es(dcols) + dx.numel() * _es(dx))
+    return dx
+
+
+def conv3s1_im2col(x, shape, out=None):
+    """Gather of nn.Conv2d(cin, cout, 3, 1, 1)'s operand (fcnhead.py:19) from NHWC rows x [B*H*W, cin]
+    (cin % 8 == 0): cols [B*H*W, 9*cin] in x.dtype, columns (kh, kw, c) like conv3s2_im2col."""
+    B, H, W = shape
+    cin = x.shape[1]
+    if out is None:
+        out = torch.empty(B * H * W, conv3s2_kp(cin), device=x.device, dtype=x.dtype)
+    check(lib.dfm_conv3s1_im2col(dtype_code(x), B, H, W, cin, ptr(x), ld(x), ptr(out), ld(out), stream()),
+          "dfm_conv3s1_im2col")
+    if ACCOUNT is not None:
+        _acct(0, B * H * W * cin * _es(x) * (1 + 9))
+    return out
+
+
+def conv3s1_col2im(dcols, shape, cin, dx=None, accumulate=False):
+    """Backward of conv3s1_im2col: dx [B*H*W, cin] (+)= the fixed-order sum of every pixel's taps."""
+    B, H, W = shape
+    if dx is None:
+        dx = torch.empty(B * H * W, cin, device=dcols.device, dtype=dcols.dtype)
+        accumulate = False
+    check(lib.dfm_conv3s1_col2im(dtype_code(dcols), B, H, W, cin, ptr(dcols), ld(dcols), ptr(dx), ld(dx),
+                                 int(accumulate), stream()), "dfm_conv3s1_col2im")
+    if ACCOUNT is not None:
+        _acct(0, B * H * W * cin * _es(dcols) * (9 + 1 + bool(accumulate)))
     return dx
 
 

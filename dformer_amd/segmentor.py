@@ -5,12 +5,14 @@ backbone's `(outs, None)` tuple is indexed before the decode head (the reference
 tuple through and crashes, SURVEY.md §3.0 #2 — the intended upstream semantics are reproduced).
 `out` is the full-resolution logits (bilinear, align_corners=False); during training it is only
 materialised when `return_logits` is True (the loss itself is fused and never needs it).
+With `decoder == "ham"` and a non-zero `cfg.aux_rate` an auxiliary FCNHead reads the stage-2 map and the
+training loss is CE(main) + aux_rate * CE(aux) (builder.py:138-143, 204-207, 231-232); no eval path runs it.
 """
 import torch
 import torch.nn as nn
 
 from . import kernels as K
-from .decoders import DecoderHead, LightHamHead, SegLossFn, _nhwc_rows
+from .decoders import DecoderHead, FCNHead, LightHamHead, SegLossFn, _nhwc_rows
 from .encoder import DFormer_Base, DFormer_Large, DFormer_Small, DFormer_Tiny
 from .functional import invalidate_weights
 
@@ -32,6 +34,15 @@ def _check_criterion(criterion, ignore_index):
             f"EncoderDecoder: the fused segmentation loss implements CrossEntropyLoss(reduction='none', "
             f"ignore_index={ignore_index}) without class weights or label smoothing (utils/train.py:189-194); "
             f"got {criterion!r}")
+
+
+def _aux_rate(cfg):
+    """cfg.aux_rate, 0 when the config has no such name (a dict-backed config raises KeyError)."""
+    try:
+        rate = getattr(cfg, "aux_rate")
+    except (AttributeError, KeyError):
+        return 0
+    return 0 if rate is None else rate
 
 
 class EncoderDecoder(nn.Module):
@@ -56,6 +67,14 @@ class EncoderDecoder(nn.Module):
         else:
             raise NotImplementedError(f"decoder {cfg.decoder!r} is outside the hot path (SURVEY.md §2)")
         self.aux_head = None
+        self.aux_rate = 0
+        if cfg.decoder == "ham" and _aux_rate(cfg) != 0:
+            # builder.py:138-143: FCNHead(self.channels[2], cfg.num_classes, ...) binds cfg.num_classes to
+            # the hidden width `channels`; the head's own num_classes stays 40 whatever the config says
+            self.aux_index = 2
+            self.aux_rate = _aux_rate(cfg)
+            self.aux_head = FCNHead(self.channels[2], cfg.num_classes, norm_layer=norm_layer, bn_eps=bn_eps,
+                                    bn_momentum=bn_mom, syncbn=syncbn)
         _check_criterion(criterion, getattr(cfg, "background", 255))
         self.criterion = criterion
         self.ignore_index = getattr(cfg, "background", 255)
@@ -70,10 +89,17 @@ class EncoderDecoder(nn.Module):
         invalidate_weights()
         return r
 
-    def _low_logits(self, rgb, modal_x):
+    def _low_logits(self, rgb, modal_x, with_aux=False):
+        """The decode head's low-resolution logits; with_aux (training with an aux head) also the aux
+        head's (builder.py:204-206). Every eval path leaves the aux head out: the reference computes its
+        logits there and throws them away."""
         outs = self.encoder_backbone(rgb, modal_x)[0]
         K.TAG = "decoder"
-        return self.decode_head.forward(outs)
+        low = self.decode_head.forward(outs)
+        if not with_aux:
+            return low
+        K.TAG = "aux"
+        return low, self.aux_head(outs[self.aux_index])
 
     def _low_rows(self, rgb, modal_x):
         """The low-res logits as NHWC rows: ([B*h*w, ncls], (B, h, w))."""
@@ -97,11 +123,19 @@ class EncoderDecoder(nn.Module):
         return K.seg_predict(rows, B, h, w, rows.shape[1], tuple(rgb.shape[-2:]))
 
     def forward(self, rgb, modal_x=None, label=None):
-        low = self._low_logits(rgb, modal_x)
         if label is None:
-            return self._upsample(low, rgb.shape[-2:])
+            return self._upsample(self._low_logits(rgb, modal_x), rgb.shape[-2:])
+        aux = None
+        if self.aux_head is not None:
+            low, aux = self._low_logits(rgb, modal_x, with_aux=True)
+        else:
+            low = self._low_logits(rgb, modal_x)
         rows, (B, h, w) = _nhwc_rows(low)
         K.TAG = "loss"
         loss = SegLossFn.apply(rows.contiguous(), B, h, w, label.long(), self.ignore_index)
+        if aux is not None:  # builder.py:231-232: + aux_rate * CE(up(aux)) over the same valid pixels
+            arows, (B, ah, aw) = _nhwc_rows(aux)
+            loss = loss + self.aux_rate * SegLossFn.apply(arows.contiguous(), B, ah, aw, label.long(),
+                                                          self.ignore_index)
         out = self._upsample(low.detach(), rgb.shape[-2:]) if self.return_logits else low
         return loss, out

@@ -21,10 +21,25 @@ from .functional import invalidate_weights, register_grad_slot, register_shadow
 from .streams import join_streams
 
 
+def _reference_modules(module, seen=None):
+    """module.modules(), except that a module declaring `reference_children` (the order in which the
+    reference registers its children, where this package's differs) is walked in that order."""
+    seen = set() if seen is None else seen
+    if id(module) in seen:
+        return
+    seen.add(id(module))
+    yield module
+    kids = module._modules
+    first = [n for n in getattr(module, "reference_children", ()) if n in kids]
+    for n in first + [n for n in kids if n not in first]:
+        if kids[n] is not None:
+            yield from _reference_modules(kids[n], seen)
+
+
 def group_weight(module, norm_layer=nn.BatchNorm2d):
     """(decay, no_decay) parameter lists exactly as init_func.group_weight builds them."""
     decay, no_decay = [], []
-    for m in module.modules():
+    for m in _reference_modules(module):
         if isinstance(m, nn.Linear):
             decay.append(m.weight)
             if m.bias is not None:

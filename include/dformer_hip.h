@@ -408,6 +408,18 @@ int dfm_conv3s2_col2im(int dtype, int B, int H, int W, int Cin, const void* dcol
  * strides (sb, sc, sh, sw) — the input gradient of the stem's first conv. */
 int dfm_conv3s2_col2im_nchw(int dtype, int dtype_out, int B, int H, int W, int Cin, const void* dcols, long ldc,
                             void* dx, long sb, long sc, long sh, long sw, dfm_stream_t stream);
+/* Dense 3x3 stride-1 pad-1 conv of the auxiliary FCN head (fcnhead.py:19) on NHWC rows, as gather +
+ * dfm_gemm like the stride-2 pair above; no folded BN / GELU (the input is a Block output).
+ * im2col (fcnhead.py:19): cols[p][(kh*3+kw)*Cin + c] = x[row of (b, y-1+kh, x-1+kw)][c], zero outside
+ *   the image; p = (b*H + y)*W + x, rows of x `ldx` and of cols `ldc` elements apart. Same column
+ *   order and Kp rule as dfm_conv3_weight_pack: Cin % 8 == 0 is required, so Kp == 9*Cin.
+ * col2im (fcnhead.py:19, backward data): dx[p][c] (+)= sum over the <= 9 taps of p of dcols, fixed
+ *   order, one owner per element (bit-reproducible, no atomics).
+ * x / cols / dcols / dx in `dtype`, 16-byte aligned, row strides multiples of 8. */
+int dfm_conv3s1_im2col(int dtype, int B, int H, int W, int Cin, const void* x, long ldx, void* cols, long ldc,
+                       dfm_stream_t stream);
+int dfm_conv3s1_col2im(int dtype, int B, int H, int W, int Cin, const void* dcols, long ldc, void* dx, long lddx,
+                       int accumulate, dfm_stream_t stream);
 int dfm_conv3_weight_pack(int dtype_out, int Cout, int Cin, int Kp, const float* w, void* wp,
                           dfm_stream_t stream);
 int dfm_conv3_weight_unpack(int Cout, int Cin, int Kp, const float* dwp, float* dw, int accumulate,
