@@ -160,6 +160,9 @@ _SIGS = {
     "dfm_seg_confusion": (c_int, [c_long, c_int, P, P, c_int, P, P]),
     "dfm_seg_predict": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_long, c_int, c_int, P, P, c_int, P, P]),
     "dfm_rows_argmax": (c_int, [c_long, c_int, P, P, P]),
+    "dfm_laser_expand_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P]),
+    "dfm_laser_expand_bwd_workspace": (c_size_t, [c_int, c_int]),
+    "dfm_laser_expand_bwd": (c_int, [c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, P]),
     "dfm_nmf_update": (c_int, [c_long, P, P, P, c_float, P, P, c_int, P]),
     "dfm_nmf_update_bwd": (c_int, [c_long, P, P, P, P, P, c_float, P, c_int, P, P, P, c_int, P]),
     "dfm_grad_nonfinite": (c_int, [c_long, P, P, P]),

@@ -30,10 +30,20 @@ def _strip(sd, prefix):
     return OrderedDict((k[len(prefix):] if k.startswith(prefix) else k, v) for k, v in sd.items())
 
 
-def load_pretrained_backbone(backbone, src, freeze=True):
-    """Returns (missing, unexpected) key lists like mmcv's non-strict load."""
+def load_pretrained_backbone(backbone, src, freeze=None):
+    """Returns (missing, unexpected) key lists like mmcv's non-strict load. The weights sit under
+    `state_dict_ema`, else `model` (DFormerTrav.init_weights, DFormer.py:408-415), else `state_dict`.
+    freeze=None follows the reference: DFormer freezes what it loaded, DFormerTrav does not
+    (DFormer.py:428-433, commented out)."""
     raw = _read(src)
-    sd = raw["state_dict_ema"] if "state_dict_ema" in raw else raw.get("state_dict", raw)
+    if freeze is None:
+        freeze = not getattr(backbone, "scan_input", False)
+    if "state_dict_ema" in raw:
+        sd = raw["state_dict_ema"]
+    elif "model" in raw and isinstance(raw["model"], dict):
+        sd = raw["model"]
+    else:
+        sd = raw.get("state_dict", raw)
     sd = _strip(sd, "backbone.")
     if next(iter(sd), "").startswith("module."):
         sd = _strip(sd, "module.")

@@ -16,7 +16,7 @@ import torch.nn.functional as F
 
 from . import kernels as K
 from .decoders import bn_batch_stats, bn_grad_stats, collectives_on
-from .functional import ATTN_PARAM_NAMES, AttentionFn, ConvFFNFn, gslot, invalidate_weights
+from .functional import ATTN_PARAM_NAMES, AttentionFn, ConvFFNFn, gslot, invalidate_weights, weights_epoch
 from .streams import fork, join, side_stream
 
 _EMPTY = {}
@@ -336,9 +336,7 @@ class DFormer(nn.Module):
         self.downsample_layers.append(nn.Sequential(
             nn.Conv2d(3, dims[0] // 2, 3, 2, 1), nn.BatchNorm2d(dims[0] // 2), nn.GELU(),
             nn.Conv2d(dims[0] // 2, dims[0], 3, 2, 1), nn.BatchNorm2d(dims[0])))
-        # unused by the reference forward (DFormer.py:202-203, 287-291); kept for state_dict parity
-        self.stem_e_fc1 = nn.Linear(360, 640)
-        self.stem_e_fc2 = nn.Linear(1, 480)
+        self._register_depth_front()
         self.downsample_layers_e = nn.ModuleList()
         self.downsample_layers_e.append(nn.Sequential(
             nn.Conv2d(1, dims[0] // 4, 3, 2, 1), nn.BatchNorm2d(dims[0] // 4), nn.GELU(),
@@ -361,6 +359,12 @@ class DFormer(nn.Module):
             for blk in self.stages[-1]:
                 blk.stage = f"s{i}"
             cur += depths[i]
+
+    def _register_depth_front(self):
+        """The children the reference registers between the RGB stem and the depth stem."""
+        # unused by the reference forward (DFormer.py:202-203, 287-291); kept for state_dict parity
+        self.stem_e_fc1 = nn.Linear(360, 640)
+        self.stem_e_fc2 = nn.Linear(1, 480)
         for p in (self.stem_e_fc1.weight, self.stem_e_fc1.bias, self.stem_e_fc2.weight, self.stem_e_fc2.bias):
             p.requires_grad_(False)  # never used: excluded from gradients (and DDP buckets)
 
@@ -407,7 +411,10 @@ class DFormer(nn.Module):
             x = x.unsqueeze(0)
         if x_e.dim() == 3:
             x_e = x_e.unsqueeze(2)
-        x_e = x_e[:, 0:1]
+        return self._run_stages(x, x_e[:, 0:1]), None
+
+    def _run_stages(self, x, x_e):
+        """The four stages (DFormer.py:293-304, 445-456) on the image x and the depth plane x_e [B, 1, H, W]."""
         dt = self.compute_dtype
         self._draw_drop_path(x.shape[0], x.device)
         outs = []
@@ -421,7 +428,158 @@ class DFormer(nn.Module):
             x = xh.permute(0, 3, 1, 2)  # NCHW view of the channels-last buffer
             x_e = eh.permute(0, 3, 1, 2)
             outs.append(x)
-        return outs, None
+        return outs
+
+
+class LaserExpandFn(torch.autograd.Function):
+    """The collapsed Attention1Dto2D (DFormer.py:308-339) on csrc/laser.hip: scans [B, N] and the folded
+    (alpha [L, Hh], g [Hh], c [1]) -> the depth plane [B, Hout, L], float32, constant along Hout.
+    Backward: dalpha, dg, dc by fixed-order sums. The scan is input data: it gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, scan, alpha, g, c, hout):
+        save = any(ctx.needs_input_grad[1:4])
+        plane, _, mean, var = K.laser_expand_fwd(scan, alpha, g, c, hout, save=save)
+        if save:
+            ctx.save_for_backward(g, mean, var)
+        return plane
+
+    @staticmethod
+    def backward(ctx, dplane):
+        K.TAG = "laser.bwd"
+        g, mean, var = ctx.saved_tensors
+        _, dalpha, dg, dc = K.laser_expand_bwd(dplane.contiguous(), g, mean, var)
+        return None, dalpha, dg, dc, None
+
+
+class _MHAParams(nn.Module):
+    """The parameters of an nn.MultiheadAttention(embed_dim, num_heads) under its state-dict keys
+    (in_proj_weight, in_proj_bias, out_proj.*), initialised like it. A container: it has no forward."""
+
+    def __init__(self, embed_dim):
+        super().__init__()
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * embed_dim, embed_dim))
+        self.in_proj_bias = nn.Parameter(torch.zeros(3 * embed_dim))
+        self.out_proj = nn.Linear(embed_dim, embed_dim)
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        nn.init.zeros_(self.out_proj.bias)
+
+
+class Attention1Dto2D(nn.Module):
+    """The laser-scan expansion of DFormerTrav (DFormer.py:308-339), with the reference's constructor
+    and state-dict keys. forward(x [B, 1, N]) -> [B, 1, output_len, mid_len] float32.
+
+    What the reference computes collapses: attn2 attends over one key, so its softmax is
+    1 and the plane is constant along output_len (query2 and attn2's Q / K projections have no effect);
+    input_proj is Linear(1, E), so attn1's scores are alpha[l, h] * x[j] + const. fold() forms
+    (alpha, g, c) from the parameters by differentiable tensor ops in float64; LaserExpandFn does the
+    B * L * Hh * N exponentials and the one plane write."""
+
+    def __init__(self, input_len=360, mid_len=640, output_len=480, embed_dim=64, num_heads=4):
+        super().__init__()
+        if embed_dim % num_heads != 0 or not 1 <= num_heads <= 8:
+            raise ValueError(f"Attention1Dto2D: embed_dim {embed_dim} / num_heads {num_heads} (1..8 heads)")
+        if input_len > K.LASER_MAX_N:
+            raise ValueError(f"Attention1Dto2D: input_len {input_len} exceeds the kernel's {K.LASER_MAX_N} ranges")
+        self.input_len = input_len  # documentation only in the reference: any scan length runs
+        self.embed_dim = embed_dim
+        self.num_heads = num_heads
+        self.mid_len = mid_len
+        self.output_len = output_len
+        self.input_proj = nn.Linear(1, embed_dim)
+        self.query1 = nn.Parameter(torch.randn(mid_len, embed_dim))
+        self.attn1 = _MHAParams(embed_dim)
+        self.query2 = nn.Parameter(torch.randn(output_len, embed_dim))
+        self.attn2 = _MHAParams(embed_dim)
+        self.output_proj = nn.Linear(embed_dim, 1)
+        self._folded = None
+
+    def fold(self):
+        """(alpha [L, Hh], g [Hh], c [1]) float32 from the parameters, differentiable:
+        alpha[l, h] = (W_q query1[l] + b_q)_h . (W_k w_in)_h / sqrt(dh);  u = W_o1^T W_v2^T W_o2^T w_out;
+        g[h] = u_h . (W_v w_in)_h;  c = u . (W_v b_in + b_v) + w_out . (W_o2 (W_v2 b_o1 + b_v2) + b_o2) + b_out.
+        The K third of attn1.in_proj_bias cancels in the softmax and query2 / attn2's Q and K thirds are
+        multiplied by a softmax over one key: their gradients are exact zeros, as in the reference."""
+        E, Hh = self.embed_dim, self.num_heads
+        dh = E // Hh
+        d = torch.float64
+        w_in, b_in = self.input_proj.weight.to(d)[:, 0], self.input_proj.bias.to(d)
+        w1, b1 = self.attn1.in_proj_weight.to(d), self.attn1.in_proj_bias.to(d)
+        w2, b2 = self.attn2.in_proj_weight.to(d), self.attn2.in_proj_bias.to(d)
+        wq, wk, wv, bq, bv = w1[:E], w1[E:2 * E], w1[2 * E:], b1[:E], b1[2 * E:]
+        wv2, bv2 = w2[2 * E:], b2[2 * E:]
+        wo1, bo1 = self.attn1.out_proj.weight.to(d), self.attn1.out_proj.bias.to(d)
+        wo2, bo2 = self.attn2.out_proj.weight.to(d), self.attn2.out_proj.bias.to(d)
+        w_out, b_out = self.output_proj.weight.to(d)[0], self.output_proj.bias.to(d)
+        q = self.query1.to(d) @ wq.t() + bq
+        alpha = (q.view(-1, Hh, dh) * (wk @ w_in).view(Hh, dh)).sum(-1) / dh ** 0.5
+        u = wo1.t() @ (wv2.t() @ (wo2.t() @ w_out))
+        g = (u.view(Hh, dh) * (wv @ w_in).view(Hh, dh)).sum(-1)
+        c = u @ (wv @ b_in + bv) + w_out @ (wo2 @ (wv2 @ bo1 + bv2) + bo2) + b_out
+        c = c + 0.0 * self.query2.to(d).sum()  # no effect on the output: an exact-zero gradient, not None
+        return alpha.float().contiguous(), g.float().contiguous(), c.float().reshape(1)
+
+    def folded(self):
+        """fold(), cached across no-grad calls until invalidate_weights() (load_state_dict, optimizer step)."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return self.fold()
+        key = (weights_epoch(), self.query1.device, self.query1.data_ptr())
+        if self._folded is None or self._folded[0] != key:
+            with torch.no_grad():
+                self._folded = (key, self.fold())
+        return self._folded[1]
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("dformer_amd runs on the HIP library only (tensors must be on the GPU)")
+        B = x.shape[0]
+        scan = x.reshape(B, -1).float().contiguous()  # DFormer.py:325-326: [B, 1, N] -> N ranges per image
+        alpha, g, c = self.folded()
+        K.TAG = "laser"
+        plane = LaserExpandFn.apply(scan, alpha, g, c, self.output_len)
+        return plane.view(B, 1, self.output_len, self.mid_len)
+
+
+class DFormerTrav(DFormer):
+    """The traversability backbone (DFormer.py:342-457): DFormer whose depth plane is the expansion of a
+    laser scan. Children in the reference's order (downsample_layers, attn_expand_e, downsample_layers_e,
+    stages), no stem_e_fc*; forward(x, x_e) takes the scan x_e [B, 1, N] and returns the list outs.
+    expand = (input_len, mid_len, output_len) of the expansion (the reference's are fixed at 360, 640, 480)."""
+
+    scan_input = True  # modal_x is a scan: it cannot be resized, cropped or flipped (evaluate.py)
+
+    def __init__(self, depths=(2, 2, 8, 2), dims=(32, 64, 128, 256), out_indices=(0, 1, 2, 3), windows=(7, 7, 7, 7),
+                 norm_cfg=None, mlp_ratios=(8, 8, 4, 4), num_heads=(2, 4, 10, 16), last_block=(50, 50, 50, 50),
+                 drop_path_rate=0.1, init_cfg=None, expand=(360, 640, 480)):
+        self.expand = tuple(expand)  # read by _register_depth_front during DFormer.__init__
+        super().__init__(depths=depths, dims=dims, out_indices=out_indices, windows=windows, norm_cfg=norm_cfg,
+                         mlp_ratios=mlp_ratios, num_heads=num_heads, last_block=last_block,
+                         drop_path_rate=drop_path_rate, init_cfg=init_cfg)
+
+    def _register_depth_front(self):
+        n, mid, out = self.expand
+        self.attn_expand_e = Attention1Dto2D(input_len=n, mid_len=mid, output_len=out, embed_dim=64, num_heads=4)
+
+    def forward(self, x, x_e):
+        if x_e is None:
+            raise ValueError("DFormerTrav: the laser scan x_e [B, 1, N] is required")
+        if x.dim() == 3:
+            x = x.unsqueeze(0)
+        elif x.dim() == 5:  # DFormer.py:440-442
+            x = x.reshape(-1, *x.shape[2:])
+        B = x.shape[0]
+        if x_e.numel() % B != 0:
+            raise ValueError(f"DFormerTrav: scans {tuple(x_e.shape)} do not match {B} images")
+        exp = self.attn_expand_e
+        if (exp.output_len, exp.mid_len) != tuple(x.shape[-2:]):
+            raise ValueError(f"DFormerTrav: the expansion's plane {exp.output_len} x {exp.mid_len} does not match "
+                             f"the image {tuple(x.shape[-2:])}")
+        return self._run_stages(x, exp(x_e.reshape(B, 1, -1)))
+
+
+def get_DFormerTrav(pretrained=False, drop_path_rate=0.1, **kwargs):
+    return DFormerTrav(dims=[64, 128, 256, 512], mlp_ratios=[8, 8, 4, 4], depths=[3, 3, 12, 2],
+                       num_heads=[1, 2, 4, 8], windows=[0, 7, 7, 7], drop_path_rate=drop_path_rate, **kwargs)
 
 
 def DFormer_Tiny(pretrained=False, **kwargs):

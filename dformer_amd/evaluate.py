@@ -138,9 +138,24 @@ def _slide_config(config, crop_size=None, stride_rate=None, crop_batch=None):
     return _Slide(crop, slide_strides(crop, stride_rate), crop_batch)
 
 
+def _scan_model(model):
+    """True when the model's modal_x is a laser scan (the DFormerTrav backbone), not a depth image."""
+    return bool(getattr(getattr(model, "encoder_backbone", None), "scan_input", False))
+
+
+def _no_scan(model, what):
+    """A scan [B, 1, N] cannot be resized, cropped or flipped with the image. The reference does nothing
+    definite there: slide_inference asserts equal image / modal_x sizes (val_mm.py:293) and evaluate_msf
+    interpolates and flips modal_x as a 4-D image (val_mm.py:362-372, 386-388), both of which fail on a scan."""
+    if _scan_model(model):
+        raise NotImplementedError(f"{what}: the DFormerTrav backbone reads a laser scan, which cannot be resized, "
+                                  "cropped or flipped; evaluate at scale 1 without flip or sliding windows")
+
+
 def _slide_low_rows(model, x, e, slide):
     """The low-res logits of every sliding window of the scaled (and flipped) inputs x, e:
     ([G*B*h*w, ncls] rows, window-major, (B, h, w), (Hs, Ws) of the image the windows were cut from)."""
+    _no_scan(model, "sliding-window inference")
     hc, wc = slide.crop
     if hc > x.shape[2] or wc > x.shape[3]:  # val_mm.py:280-286: both dimensions go to the crop size
         x = K.resize_nchw(x, (hc, wc), True)
@@ -179,12 +194,15 @@ def msf_scores(model, rgb, modal_x, num_classes, scales, flip, out_shape=None, c
         raise ValueError(f"msf_scores: batch of the images {rgb.shape[0]} != labels {B}")
     if crop_size is not None:
         slide = _slide_config(None, crop_size, stride_rate, crop_batch)
+    scan = _scan_model(model)
+    if scan and (slide is not None or flip or any(msf_size(H, W, s) != (H, W) for s in scales)):
+        _no_scan(model, "multi-scale / flip / sliding-window evaluation")
     acc = torch.zeros(B * H * W, num_classes, device=rgb.device, dtype=torch.float32)
     for scale in scales:
         size = msf_size(H, W, scale)
         for f in ((False, True) if flip else (False,)):
             x = K.resize_nchw(rgb, size, True, flip=f)
-            e = K.resize_nchw(modal_x, size, True, flip=f)
+            e = modal_x if scan else K.resize_nchw(modal_x, size, True, flip=f)
             if slide is not None:
                 rows, (b, h, w), scaled = _slide_low_rows(model, x, e, slide)
                 K.slide_msf_accumulate(rows, b, h, w, num_classes, slide.crop, slide.strides, scaled, (H, W), f, acc)
@@ -246,14 +264,17 @@ def _write_pred_png(path, pred, palette):
     Image.fromarray(pred if palette is None else palette[pred]).save(path)
 
 
-def _batch_inputs(batch, device):
+def _batch_inputs(batch, device, scan=False):
     """val_mm.py:41-52, 115-125: rgb, depth ('laser', the reference's key here, else 'modal_x') and gt of
-    a batch on the device; an unbatched sample gets its batch axis."""
+    a batch on the device; an unbatched sample gets its batch axis. scan: modal_x holds laser scans
+    (DFormerTrav), one per image: [B, 1, N] whatever axes the loader gave it."""
     rgb, gt = batch["rgb"], batch["gt"]
     modal_x = batch["laser"] if "laser" in batch else batch["modal_x"]
     if rgb.dim() == 3:
         rgb = rgb.unsqueeze(0)
-    if modal_x.dim() == 3:
+    if scan:
+        modal_x = modal_x.reshape(rgb.shape[0], 1, -1)
+    elif modal_x.dim() == 3:
         modal_x = modal_x.unsqueeze(0)
     if gt.dim() == 2:
         gt = gt.unsqueeze(0)
@@ -264,11 +285,14 @@ def _run(model, dataloader, config, device, engine, sliding, step):
     """The loop of evaluate_msf, evaluate and save_preds: step(metrics, slide, batch, rgb, modal_x, gt) per
     batch, slide being config's sliding-window settings (None unless sliding). Returns the Metrics (a list
     of every rank's Metrics when engine.distributed, like the reference)."""
+    if sliding:
+        _no_scan(model, "sliding-window evaluation")
     slide = _slide_config(config) if sliding else None  # a bad rate fails before the first batch
     model.eval()
     metrics = Metrics(config.num_classes, config.background, device)
+    scan = _scan_model(model)
     for batch in dataloader:
-        step(metrics, slide, batch, *_batch_inputs(batch, device))
+        step(metrics, slide, batch, *_batch_inputs(batch, device, scan))
     if engine is not None and getattr(engine, "distributed", False):
         all_metrics = [None for _ in range(engine.world_size)]
         torch.distributed.all_gather_object(all_metrics, metrics)

@@ -28,6 +28,11 @@ def invalidate_weights():
     _WCACHE.clear()
 
 
+def weights_epoch():
+    """Changes whenever invalidate_weights() ran: the key of values derived from parameters."""
+    return _EPOCH[0]
+
+
 def register_shadow(p, shadow):
     """The fused optimizer keeps `shadow` (bf16 copy of p) up to date itself."""
     _WCACHE[(id(p), shadow.dtype)] = (_EPOCH[0], shadow, (p.data_ptr(),), (weakref.ref(p),))

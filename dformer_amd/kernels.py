@@ -989,6 +989,61 @@ def rows_argmax(acc, ncls, out=None):
     return out
 
 
+# ------------------------------------------------------------------- laser-scan expansion (Trav)
+LASER_MAX_N = 8192  # DFM_LASER_MAX_N: the ranges of one scan a workgroup stages in LDS
+
+
+def _f32c(t, what):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError(f"{what} {tuple(t.shape)} {t.dtype} is not contiguous float32")
+    return t
+
+
+def laser_expand_fwd(x, alpha, g, c, Hout, save=True):
+    """The collapsed Attention1Dto2D (DFormer.py:308-339): scans x [B, N], alpha [L, Hh], g [Hh], c [1]
+    (float32) -> (plane [B, Hout, L], s [B, L], mean, var [B, L, Hh]); mean / var are None unless save."""
+    B, N = x.shape
+    L, Hh = alpha.shape
+    for t, what in ((x, "laser_expand_fwd: scans"), (alpha, "laser_expand_fwd: alpha"), (g, "laser_expand_fwd: g"),
+                    (c, "laser_expand_fwd: c")):
+        _f32c(t, what)
+    if g.numel() != Hh or c.numel() != 1:
+        raise ValueError(f"laser_expand_fwd: g {tuple(g.shape)} / c {tuple(c.shape)} do not match {Hh} heads")
+    s = torch.empty(B, L, device=x.device, dtype=torch.float32)
+    plane = torch.empty(B, Hout, L, device=x.device, dtype=torch.float32)
+    mean = torch.empty(B, L, Hh, device=x.device, dtype=torch.float32) if save else None
+    var = torch.empty_like(mean) if save else None
+    check(lib.dfm_laser_expand_fwd(B, N, L, Hh, Hout, ptr(x), ptr(alpha), ptr(g), ptr(c), ptr(s), ptr(mean), ptr(var),
+                                   ptr(plane), stream()), "dfm_laser_expand_fwd")
+    if ACCOUNT is not None:  # per (b, l, h, j): sub, mul, exp, add, fma (+ the variance walk's sub, mul, exp, mul, fma)
+        _acct(B * L * Hh * N * (6.0 + 6.0 * save),
+              4 * (B * N + L * Hh + Hh + 1 + B * L + B * Hout * L + 2 * save * B * L * Hh), "f32")
+    return plane, s, mean, var
+
+
+def laser_expand_bwd(dplane, g, mean, var):
+    """dplane [B, Hout, L] -> (ds [B, L], dalpha [L, Hh], dg [Hh], dc [1]), fixed-order sums."""
+    B, Hout, L = dplane.shape
+    Hh = g.numel()
+    for t, what in ((dplane, "laser_expand_bwd: dplane"), (g, "laser_expand_bwd: g"), (mean, "laser_expand_bwd: mean"),
+                    (var, "laser_expand_bwd: var")):
+        _f32c(t, what)
+    if tuple(mean.shape) != (B, L, Hh) or tuple(var.shape) != (B, L, Hh):
+        raise ValueError(f"laser_expand_bwd: moments {tuple(mean.shape)} / {tuple(var.shape)} are not [{B}, {L}, {Hh}]")
+    dev = dplane.device
+    ds = torch.empty(B, L, device=dev, dtype=torch.float32)
+    dalpha = torch.empty(L, Hh, device=dev, dtype=torch.float32)
+    dg = torch.empty(Hh, device=dev, dtype=torch.float32)
+    dc = torch.empty(1, device=dev, dtype=torch.float32)
+    ws = _ws(lib.dfm_laser_expand_bwd_workspace(L, Hh), dev)
+    check(lib.dfm_laser_expand_bwd(B, L, Hh, Hout, ptr(dplane), ptr(g), ptr(mean), ptr(var), ptr(ds), ptr(dalpha),
+                                   ptr(dg), ptr(dc), ptr(ws), stream()), "dfm_laser_expand_bwd")
+    if ACCOUNT is not None:
+        _acct(B * Hout * L + 4.0 * B * L * Hh + B * L,
+              4 * (B * Hout * L + B * L + 2 * B * L * Hh + L * Hh + 2 * Hh + 1), "f32")
+    return ds, dalpha, dg, dc
+
+
 # ---------------------------------------------------------------------------------------- NMF
 def _copy_dtype(flag):
     """bf16_copy argument: False / None (no copy), True (bf16) or a 16-bit torch dtype."""

@@ -13,11 +13,13 @@ import torch.nn as nn
 
 from . import kernels as K
 from .decoders import DecoderHead, FCNHead, LightHamHead, SegLossFn, _nhwc_rows
-from .encoder import DFormer_Base, DFormer_Large, DFormer_Small, DFormer_Tiny
+from .encoder import DFormer_Base, DFormer_Large, DFormer_Small, DFormer_Tiny, get_DFormerTrav
 from .functional import invalidate_weights
 
 BACKBONES = {"DFormer-Tiny": (DFormer_Tiny, [32, 64, 128, 256]), "DFormer-Small": (DFormer_Small, [64, 128, 256, 512]),
-             "DFormer-Base": (DFormer_Base, [64, 128, 256, 512]), "DFormer-Large": (DFormer_Large, [96, 192, 288, 576])}
+             "DFormer-Base": (DFormer_Base, [64, 128, 256, 512]), "DFormer-Large": (DFormer_Large, [96, 192, 288, 576]),
+             # builder.py:109-111: modal_x is a laser scan [B, 1, 360], expanded to the depth plane
+             "DFormerTrav-Base": (get_DFormerTrav, [64, 128, 256, 512])}
 
 
 def _check_criterion(criterion, ignore_index):
@@ -93,7 +95,9 @@ class EncoderDecoder(nn.Module):
         """The decode head's low-resolution logits; with_aux (training with an aux head) also the aux
         head's (builder.py:204-206). Every eval path leaves the aux head out: the reference computes its
         logits there and throws them away."""
-        outs = self.encoder_backbone(rgb, modal_x)[0]
+        outs = self.encoder_backbone(rgb, modal_x)
+        if isinstance(outs, tuple):  # DFormer returns (outs, None), DFormerTrav the list itself
+            outs = outs[0]
         K.TAG = "decoder"
         low = self.decode_head.forward(outs)
         if not with_aux:

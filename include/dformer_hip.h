@@ -474,6 +474,35 @@ int dfm_seg_predict(int dtype, int B, int h, int w, int ncls, const void* low, l
                     dfm_stream_t stream);
 int dfm_rows_argmax(long npix, int ncls, const float* acc, unsigned char* pred, dfm_stream_t stream);
 
+/* ---------------------------------------------------------------- laser-scan expansion (DFormerTrav)
+ * models/encoders/DFormer.py:308-339 Attention1Dto2D (called at DFormer.py:444), collapsed: attn2 attends
+ * over ONE key (softmax = 1), so the returned plane [B, 1, Hout, L] is constant along Hout, and input_proj
+ * is Linear(1, E), so attn1's scores are affine in the scalar range. With alpha [L][Hh], g [Hh], c [1]
+ * folded from the module's parameters (float32, on the device):
+ *   mean[b][l][h] = sum_j softmax_j(alpha[l][h] * x[b][j]) * x[b][j]          x [B][N]: the scans
+ *   var[b][l][h]  = sum_j softmax_j(alpha[l][h] * x[b][j]) * (x[b][j] - mean[b][l][h])^2
+ *   s[b][l] = c + sum_h g[h] * mean[b][l][h];   plane[b][y][l] = s[b][l] for every y < Hout
+ * laser_expand_fwd writes s [B][L], plane [B][Hout][L] and, unless both are NULL (inference), the moments
+ *   mean / var [B][L][Hh] the backward needs. A workgroup stages one scan in LDS: N <= DFM_LASER_MAX_N.
+ *   Any L, Hout >= 1; 1 <= Hh <= 8; B <= 65535. All float32.
+ * laser_expand_bwd, from dplane [B][Hout][L]:
+ *   ds[b][l]     = sum_y dplane[b][y][l]   (8 contiguous chunks of rows, each summed in ascending y, the
+ *                                           chunks combined in ascending order)
+ *   dalpha[l][h] = g[h] * sum_b ds[b][l] * var[b][l][h]      (ascending b)
+ *   dg[h]        = sum_{b,l} ds[b][l] * mean[b][l][h],   dc[0] = sum_{b,l} ds[b][l]
+ *                  (over b first, then per workgroup of 256 (l, h) pairs in ascending order, then the
+ *                  workgroups' partials in ascending order; workspace: dfm_laser_expand_bwd_workspace bytes)
+ *   Every sum runs in a fixed order, without float atomics: two runs agree bit for bit. The scan is input
+ *   data: its gradient is not computed.
+ * New symbols only: dfm_abi_version() stays 13. */
+#define DFM_LASER_MAX_N 8192
+int dfm_laser_expand_fwd(int B, int N, int L, int Hh, int Hout, const float* x, const float* alpha, const float* g,
+                         const float* c, float* s, float* mean, float* var, float* plane, dfm_stream_t stream);
+size_t dfm_laser_expand_bwd_workspace(int L, int Hh); /* 0: unsupported L / Hh */
+int dfm_laser_expand_bwd(int B, int L, int Hh, int Hout, const float* dplane, const float* g, const float* mean,
+                         const float* var, float* ds, float* dalpha, float* dg, float* dc, void* workspace,
+                         dfm_stream_t stream);
+
 /* ---------------------------------------------------------------- NMF2D multiplicative update
  * ham_head.py:120-145:  out = a * num / (den + eps)  (float32), and its backward:
  *   ga (+= when accumulate_ga) = g * num / (den+eps);  gnum = g * a / (den+eps);
