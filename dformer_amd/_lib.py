@@ -175,6 +175,22 @@ _SIGS = {
     "dfm_seg_loss_grad_partials_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "dfm_seg_loss_fwd_grad": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P, P, P]),
     "dfm_seg_loss_bwd_gather": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "dfm_fss_footprint_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "dfm_fss_mask_footprint": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "dfm_fss_proto_pool_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_long, P, P, P, P, P]),
+    "dfm_fss_proto_pool_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, c_long, P]),
+    "dfm_fss_sim_fwd": (c_int, [c_int, c_int, c_int, c_int, P, c_long, P, c_float, P, P, P, P, P]),
+    "dfm_fss_sim_bwd_workspace": (c_size_t, [c_int, c_int]),
+    "dfm_fss_sim_bwd": (c_int, [c_int, c_int, c_int, c_int, P, c_long, P, c_float, P, P, P, P, P, P, c_long, c_int,
+                                P, P, P]),
+    "dfm_fss_loss_workspace": (c_size_t, []),
+    "dfm_fss_loss_fwd": (c_int, [c_int, c_int, c_int, c_int, P, c_long, c_int, c_int, P, c_int, c_int, P, c_float, P,
+                                 P, P, P]),
+    "dfm_fss_loss_bwd_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dfm_fss_loss_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_float, P, P, P,
+                                 P]),
+    "dfm_fss_fuse_fwd": (c_int, [c_int, c_int, c_int, c_int, P, c_long, c_int, c_int, P, c_int, c_int, c_float, P,
+                                 P]),
     "dfm_adamw": (c_int, [c_long, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_float, P, c_int,
                           P]),
     "dfm_adamw_dev": (c_int, [c_long, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, P, c_int, P]),

@@ -879,3 +879,68 @@ class SegLossFn(torch.autograd.Function):
         if logits_rows.dtype != torch.float32:
             dl = K.cast(dl, logits_rows.dtype)
         return dl, None, None, None, None, None
+
+
+# ============================================================================ few-shot episodes
+class FssProtoSimFn(torch.autograd.Function):
+    """The prototype branch of meta_forward (builder.py:273-297) on the stage-3 map of the concatenated
+    batch, f3 [B*S + B, C, h', w'] (an NCHW view of NHWC rows, supports first): masked average pooling of the
+    support rows by the mask footprints, the mean over shots, and softmax(20 cos(query, proto) / T).
+    Returns (the query slice of f3 for the decode head, prob [B*h'*w', 2] float32, proto [B, 2, C] float32).
+    The backward writes the stage-3 gradient as one buffer: the support rows from the prototypes, the query
+    rows from the decode head's gradient plus the similarity's (accumulated in place)."""
+
+    @staticmethod
+    def forward(ctx, f3, foot, count, B, S, temperature):
+        rows, (N, hs, ws) = _nhwc_rows(f3)
+        cells, ns = hs * ws, B * S * hs * ws
+        sup, qry = rows[:ns], rows[ns:]
+        proto, wgt = K.fss_proto_pool_fwd(sup, foot, count, B, S)
+        need = ctx.needs_input_grad[0]
+        prob, saved = K.fss_sim_fwd(qry, proto, temperature, save=need)
+        if need:
+            ctx.save_for_backward(qry, proto, prob, wgt, *saved)
+        ctx.meta = (B, S, N, hs, ws, cells, temperature)
+        ctx.mark_non_differentiable(proto)
+        return f3[B * S:], prob, proto
+
+    @staticmethod
+    def backward(ctx, dq_map, dprob, _dproto):
+        K.TAG = "fss.bwd"
+        qry, proto, prob, wgt, cosv, qnorm, pnorm = ctx.saved_tensors
+        B, S, N, hs, ws, cells, temperature = ctx.meta
+        C = qry.shape[1]
+        df = torch.empty(N * cells, C, device=qry.device, dtype=qry.dtype)
+        dq = df[B * S * cells:]
+        if dq_map is not None:
+            dq.view(B, hs, ws, C).copy_(dq_map.permute(0, 2, 3, 1))
+        if dprob is None:
+            dprob = torch.zeros_like(prob)
+        _, dproto = K.fss_sim_bwd(qry, proto, dprob.contiguous(), prob, (cosv, qnorm, pnorm), temperature, dq=dq,
+                                  accumulate=dq_map is not None)
+        K.fss_proto_pool_bwd(wgt, dproto, B, S, df.dtype, out=df[:B * S * cells])
+        return df.view(N, hs, ws, C).permute(0, 3, 1, 2), None, None, None, None, None
+
+
+class FssLossFn(torch.autograd.Function):
+    """CE(alpha * up(low) + (1 - alpha) * up(prob), label)[label != 255].mean() (builder.py:298-308), fused:
+    neither upsampled map is materialised. low_rows [B*h*w, 2], prob [B*h'*w', 2] float32."""
+
+    @staticmethod
+    def forward(ctx, low_rows, prob, B, h, w, hs, ws, label, alpha):
+        label = label.contiguous()
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        out, gplane = K.fss_loss_fwd(low_rows, B, h, w, prob, hs, ws, label, alpha, save=need)
+        if need:
+            ctx.save_for_backward(gplane, out)
+        ctx.meta = (B, h, w, hs, ws, alpha, low_rows.dtype)
+        return out[0] / out[1].clamp_min(1.0)
+
+    @staticmethod
+    def backward(ctx, g):
+        K.TAG = "fss.bwd"
+        gplane, out = ctx.saved_tensors
+        B, h, w, hs, ws, alpha, dtype = ctx.meta
+        dlow, dprob = K.fss_loss_bwd(gplane, B, h, w, hs, ws, out, alpha, dtype,
+                                     gscale=g.reshape(1).float().contiguous())
+        return dlow, dprob, None, None, None, None, None, None, None

@@ -355,6 +355,48 @@ def evaluate(model, dataloader, config, device, engine=None, save_dir=None, slid
     return _run(model, dataloader, config, device, engine, sliding, step)
 
 
+FSS_KEYS = ("s_img", "s_depth", "s_gt", "q_img", "q_depth", "q_gt")
+
+
+def _episode_inputs(batch, device):
+    """val_mm.py:222-227: the six tensors of an episode batch on the device, in meta_forward's order plus q_gt."""
+    missing = [k for k in FSS_KEYS if k not in batch]
+    if missing:
+        raise KeyError(f"fss_evaluate: the batch lacks {missing} (it has {sorted(batch)})")
+    return tuple(batch[k].to(device) for k in FSS_KEYS)
+
+
+@torch.no_grad()
+def fss_evaluate(model, dataloader, config, device, engine=None, save_dir=None, palette=None):
+    """val_mm.py:210-254: eval-mode meta_forward per episode batch (keys s_img, s_gt, s_depth, q_img, q_gt,
+    q_depth and, for save_dir, fn), the fused score rows counted against q_gt. Returns the Metrics (a list of
+    every rank's when engine.distributed). save_dir writes <save_dir>/<name>_pred.png per query image:
+    coloured with `palette` (else config.palette), or the class indices as an 8-bit image."""
+    if save_dir is not None:
+        if palette is None:
+            palette = _optional(config, "palette")
+        if palette is not None:
+            palette = check_palette(palette, config.num_classes)
+    model.eval()
+    metrics = Metrics(config.num_classes, config.background, device)
+    for batch in dataloader:
+        s_rgb, s_depth, s_gt, q_rgb, q_depth, q_gt = _episode_inputs(batch, device)
+        logits = model.meta_forward(s_rgb, s_depth, s_gt, q_rgb, q_depth)  # an NCHW view of [B*H*W, 2] rows
+        if tuple(q_gt.shape) != (logits.shape[0],) + tuple(logits.shape[-2:]):
+            raise ValueError(f"fss_evaluate: q_gt {tuple(q_gt.shape)} does not match the logits {tuple(logits.shape)}")
+        rows = logits.permute(0, 2, 3, 1).reshape(-1, logits.shape[1])
+        metrics.update_rows(rows, q_gt)
+        if save_dir is not None:
+            pred = K.rows_argmax(rows, config.num_classes).view(q_gt.shape)
+            for p, fn in zip(pred.cpu().numpy(), batch["fn"]):
+                _write_pred_png(os.path.join(save_dir, pred_png_name(fn) + "_pred.png"), p, palette)
+    if engine is not None and getattr(engine, "distributed", False):
+        all_metrics = [None for _ in range(engine.world_size)]
+        torch.distributed.all_gather_object(all_metrics, metrics)
+        return all_metrics
+    return metrics
+
+
 @torch.no_grad()
 def save_preds(model, dataloader, config, device, engine=None, model_path=None, sliding=False, out_root="output"):
     """val_mm.py:25-98: the metrics of `evaluate` plus one <out_root>/<model_path>/<img_id>.npy uint8 class

@@ -1215,6 +1215,130 @@ def seg_loss_bwd_gather(part, B, h, w, ncls, loss_out, gscale, dtype):
     return dl
 
 
+# ------------------------------------------------------------- few-shot episodes (meta_forward)
+def fss_mask_footprint(mask, low_hw):
+    """int64 masks [n, H, W] -> (foot [n, 2, h', w'], count [n, 2]) float32: the adjoint of the bilinear
+    upsample (h', w') -> (H, W) applied to the indicators of classes 0 and 1, and their pixel counts."""
+    n, H, W = mask.shape
+    hs, ws = low_hw
+    if mask.dtype != torch.int64 or not mask.is_contiguous():
+        raise ValueError(f"fss_mask_footprint: masks {tuple(mask.shape)} {mask.dtype} are not contiguous int64")
+    foot = torch.empty(n, 2, hs, ws, device=mask.device, dtype=torch.float32)
+    count = torch.empty(n, 2, device=mask.device, dtype=torch.float32)
+    ws_ = _ws(lib.dfm_fss_footprint_workspace(n, hs, ws, H, W), mask.device)
+    check(lib.dfm_fss_mask_footprint(n, hs, ws, H, W, ptr(mask), ptr(foot), ptr(count), ptr(ws_), stream()),
+          "dfm_fss_mask_footprint")
+    if ACCOUNT is not None:  # per pixel and class: one compare and two tap multiply-adds per pass
+        _acct(8.0 * n * H * W, 8 * n * H * W + 4 * (foot.numel() + count.numel()), "f32")
+    return foot, count
+
+
+def fss_proto_pool_fwd(f, foot, count, B, S):
+    """Support rows f [B*S*cells, C] (row stride ld(f)) -> (proto [B, 2, C] float32, wgt [B*S*cells, 2])."""
+    rows, C = f.shape
+    cells = rows // (B * S)
+    assert rows == B * S * cells and foot.numel() == 2 * rows and count.numel() == 2 * B * S
+    wgt = torch.empty(rows, 2, device=f.device, dtype=torch.float32)
+    proto = torch.empty(B, 2, C, device=f.device, dtype=torch.float32)
+    check(lib.dfm_fss_proto_pool_fwd(dtype_code(f), B, S, cells, C, ptr(f), ld(f), ptr(_f32c(foot, "fss foot")),
+                                     ptr(_f32c(count, "fss count")), ptr(wgt), ptr(proto), stream()),
+          "dfm_fss_proto_pool_fwd")
+    if ACCOUNT is not None:
+        _acct(4.0 * rows * C, rows * C * _es(f) + 4 * (4 * rows + 2 * B * S + 2 * B * C), "f32")
+    return proto, wgt
+
+
+def fss_proto_pool_bwd(wgt, dproto, B, S, dtype, out=None):
+    """df [B*S*cells, C] (dtype; `out` when given) = wgt[:, 0] x dproto[b, 0] + wgt[:, 1] x dproto[b, 1]."""
+    rows, C = wgt.shape[0], dproto.shape[-1]
+    df = torch.empty(rows, C, device=wgt.device, dtype=dtype) if out is None else out
+    assert df.dtype == dtype and tuple(df.shape) == (rows, C)
+    check(lib.dfm_fss_proto_pool_bwd(dtype_code(df), B, S, rows // (B * S), C, ptr(wgt),
+                                     ptr(_f32c(dproto, "fss dproto")), ptr(df), ld(df), stream()),
+          "dfm_fss_proto_pool_bwd")
+    if ACCOUNT is not None:
+        _acct(3.0 * rows * C, rows * C * _es(df) + 4 * (2 * rows + 2 * B * C), "f32")
+    return df
+
+
+def fss_sim_fwd(q, proto, temperature=1.0, save=True):
+    """Query rows q [B*cells, C], proto [B, 2, C] -> (prob [B*cells, 2], saved): softmax over [bg, fg] of
+    20 cos(q, proto) / temperature; saved = (cos, qnorm, pnorm) for fss_sim_bwd (cos / qnorm None unless save)."""
+    rows, C = q.shape
+    B = proto.shape[0]
+    cells = rows // B
+    assert rows == B * cells and tuple(proto.shape) == (B, 2, C)
+    dev = q.device
+    prob = torch.empty(rows, 2, device=dev, dtype=torch.float32)
+    cosv = torch.empty(rows, 2, device=dev, dtype=torch.float32) if save else None
+    qnorm = torch.empty(rows, device=dev, dtype=torch.float32) if save else None
+    pnorm = torch.empty(B, 2, device=dev, dtype=torch.float32)
+    check(lib.dfm_fss_sim_fwd(dtype_code(q), B, cells, C, ptr(q), ld(q), ptr(_f32c(proto, "fss proto")),
+                              1.0 / temperature, ptr(prob), ptr(cosv), ptr(qnorm), ptr(pnorm), stream()),
+          "dfm_fss_sim_fwd")
+    if ACCOUNT is not None:
+        _acct(6.0 * rows * C, rows * C * _es(q) + 4 * (2 * B * C + rows * (2 + 3 * save) + 2 * B), "f32")
+    return prob, (cosv, qnorm, pnorm)
+
+
+def fss_sim_bwd(q, proto, dprob, prob, saved, temperature=1.0, dq=None, accumulate=False):
+    """(dq [B*cells, C] in q's dtype (+= into dq when accumulate), dproto [B, 2, C] float32)."""
+    rows, C = q.shape
+    B = proto.shape[0]
+    cosv, qnorm, pnorm = saved
+    if dq is None:
+        dq = torch.empty(rows, C, device=q.device, dtype=q.dtype)
+        accumulate = False
+    assert dq.dtype == q.dtype
+    dproto = torch.empty(B, 2, C, device=q.device, dtype=torch.float32)
+    ws = _ws(lib.dfm_fss_sim_bwd_workspace(B, rows // B), q.device)
+    check(lib.dfm_fss_sim_bwd(dtype_code(q), B, rows // B, C, ptr(q), ld(q), ptr(proto), 1.0 / temperature,
+                              ptr(_f32c(dprob, "fss dprob")), ptr(prob), ptr(cosv), ptr(qnorm), ptr(pnorm), ptr(dq),
+                              ld(dq), int(accumulate), ptr(dproto), ptr(ws), stream()), "dfm_fss_sim_bwd")
+    if ACCOUNT is not None:  # q is read by both the row sum and the outer product
+        _acct(10.0 * rows * C, rows * C * _es(q) * (3 + bool(accumulate)) + 4 * (4 * B * C + 7 * rows), "f32")
+    return dq, dproto
+
+
+def fss_loss_fwd(low, B, h, w, prob, hs, ws, label, alpha, save=True):
+    """low [B*h*w, >= 2] decode-head logits rows, prob [B*hs*ws, 2] float32, label int64 [B, H, W] ->
+    (loss_out = (sum, count), gplane [B, H, W] float32 or None): CE of alpha up(low) + (1 - alpha) up(prob)
+    over the pixels labelled 0 or 1."""
+    H, W = label.shape[-2:]
+    out = torch.empty(2, device=low.device, dtype=torch.float32)
+    gplane = torch.empty(B, H, W, device=low.device, dtype=torch.float32) if save else None
+    wsp = _ws(lib.dfm_fss_loss_workspace(), low.device)
+    check(lib.dfm_fss_loss_fwd(dtype_code(low), B, h, w, ptr(low), ld(low), hs, ws, ptr(_f32c(prob, "fss prob")), H, W,
+                               ptr(label), float(alpha), ptr(gplane), ptr(out), ptr(wsp), stream()), "dfm_fss_loss_fwd")
+    if ACCOUNT is not None:
+        _acct(0, B * h * w * 2 * _es(low) + prob.numel() * 4 + label.numel() * (8 + 4 * save))
+    return out, gplane
+
+
+def fss_loss_bwd(gplane, B, h, w, hs, ws, loss_out, alpha, dtype, gscale=None):
+    """(dlow [B*h*w, 2] in dtype, dprob [B*hs*ws, 2] float32) from the forward's residual plane."""
+    H, W = gplane.shape[-2:]
+    dlow = torch.empty(B * h * w, 2, device=gplane.device, dtype=dtype)
+    dprob = torch.empty(B * hs * ws, 2, device=gplane.device, dtype=torch.float32)
+    wsp = _ws(lib.dfm_fss_loss_bwd_workspace(B, h, w, hs, ws, H, W), gplane.device)
+    check(lib.dfm_fss_loss_bwd(dtype_code(dlow), B, h, w, hs, ws, H, W, ptr(gplane), ptr(loss_out), ptr(gscale),
+                               float(alpha), ptr(dlow), ptr(dprob), ptr(wsp), stream()), "dfm_fss_loss_bwd")
+    if ACCOUNT is not None:  # the plane is read once per grid
+        _acct(0, 2 * gplane.numel() * 4 + dlow.numel() * _es(dlow) + dprob.numel() * 4)
+    return dlow, dprob
+
+
+def fss_fuse(low, B, h, w, prob, hs, ws, out_hw, alpha):
+    """The fused full-resolution logits alpha up(low) + (1 - alpha) up(prob): float32 [B*H*W, 2] rows."""
+    H, W = out_hw
+    out = torch.empty(B * H * W, 2, device=low.device, dtype=torch.float32)
+    check(lib.dfm_fss_fuse_fwd(dtype_code(low), B, h, w, ptr(low), ld(low), hs, ws, ptr(_f32c(prob, "fss prob")), H, W,
+                               float(alpha), ptr(out), stream()), "dfm_fss_fuse_fwd")
+    if ACCOUNT is not None:
+        _acct(0, B * h * w * 2 * _es(low) + prob.numel() * 4 + out.numel() * 4)
+    return out
+
+
 # -------------------------------------------------------------------------------------- AdamW
 def loss_scale_update(amp, flag, growth, backoff, interval):
     check(lib.dfm_loss_scale_update(ptr(amp), ptr(flag), growth, backoff, interval, stream()),

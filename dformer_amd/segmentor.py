@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import kernels as K
-from .decoders import DecoderHead, FCNHead, LightHamHead, SegLossFn, _nhwc_rows
+from .decoders import DecoderHead, FCNHead, FssLossFn, FssProtoSimFn, LightHamHead, SegLossFn, _nhwc_rows
 from .encoder import DFormer_Base, DFormer_Large, DFormer_Small, DFormer_Tiny, get_DFormerTrav
 from .functional import invalidate_weights
 
@@ -81,6 +81,8 @@ class EncoderDecoder(nn.Module):
         self.criterion = criterion
         self.ignore_index = getattr(cfg, "background", 255)
         self.return_logits = True
+        self.keep_episode = False  # meta_forward leaves proto / prob / foot / count in self.last_episode (tests)
+        self.last_episode = None
 
     def set_compute_dtype(self, dtype):
         self.encoder_backbone.compute_dtype = dtype
@@ -143,3 +145,84 @@ class EncoderDecoder(nn.Module):
                                                           self.ignore_index)
         out = self._upsample(low.detach(), rgb.shape[-2:]) if self.return_logits else low
         return loss, out
+
+    # ------------------------------------------------------------------ few-shot episodes (builder.py:210-320)
+    def encode(self, rgb, modal_x):
+        """builder.py:210-211: the backbone's four maps (DFormer's (outs, None) tuple is indexed)."""
+        outs = self.encoder_backbone(rgb, modal_x)
+        return outs[0] if isinstance(outs, tuple) else outs
+
+    def decode(self, x, rgb):
+        """builder.py:213-222: the decode head on the maps x, upsampled to rgb's size (with an aux head, the
+        pair (out, aux) like the reference)."""
+        K.TAG = "decoder"
+        out = self._upsample(self.decode_head.forward(x), rgb.shape[-2:])
+        if self.aux_head is None:
+            return out
+        K.TAG = "aux"
+        return out, self._upsample(self.aux_head(x[self.aux_index]), rgb.shape[-2:])
+
+    def _fss_config(self):
+        """(alpha, temperature) of the episode head, after the checks meta_forward makes up front."""
+        if self.cfg.num_classes != 2:
+            raise NotImplementedError(f"meta_forward: the reference stacks exactly [bg, fg] (builder.py:296); "
+                                      f"cfg.num_classes = {self.cfg.num_classes} is not 2")
+        if self.aux_head is not None:
+            raise NotImplementedError("meta_forward: with an aux head the reference's decode returns a tuple that "
+                                      "alpha * logits cannot take (builder.py:218-221, 303); set cfg.aux_rate = 0")
+        vals = []
+        for name in ("alpha", "temperature"):
+            try:
+                v = getattr(self.cfg, name)
+            except (AttributeError, KeyError):
+                v = None
+            if v is None:
+                raise ValueError(f"meta_forward: cfg.{name} is missing (local_configs/Trav/DFormer_Base.py sets "
+                                 "alpha = 0.5, temperature = 1)")
+            vals.append(float(v))
+        if not vals[1] > 0.0:
+            raise ValueError(f"meta_forward: cfg.temperature = {vals[1]} must be positive")
+        return tuple(vals)
+
+    def meta_forward(self, s_rgb, s_depth, s_mask, q_rgb, q_depth, q_gt=None):
+        """builder.py:237-310, one few-shot episode batch: s_rgb [B, S, 3, H, W], s_depth [B, S, 1, N] (whatever
+        the backbone's modal_x is per image), s_mask [B, S, H, W] (1 = foreground, 0 = background, anything
+        else, 255 included, in neither prototype), q_rgb [B, 3, H, W], q_depth [B, 1, N], q_gt [B, H, W].
+        Returns (loss, fused_logits [B, 2, H, W]) with q_gt, fused_logits without; with return_logits False the
+        training call returns the decode head's low-res logits in place of fused_logits, as forward does.
+        The ignore label of q_gt is 255, hard-coded as in the reference (builder.py:307), not cfg.background.
+        One encoder pass over the B*S + B images; the prototype pooling, the cosine branch and the loss run on
+        stage-3 sized tensors; nothing is read back to the host."""
+        alpha, temperature = self._fss_config()
+        if s_rgb.dim() != 5 or s_mask.dim() != 4 or tuple(s_mask.shape[:2]) != tuple(s_rgb.shape[:2]):
+            raise ValueError(f"meta_forward: s_rgb {tuple(s_rgb.shape)} / s_mask {tuple(s_mask.shape)} are not "
+                             "[B, S, 3, H, W] / [B, S, H, W]")
+        B, S = s_rgb.shape[:2]
+        H, W = s_rgb.shape[-2:]
+        if q_rgb.shape[0] != B or tuple(q_rgb.shape[-2:]) != (H, W) or tuple(s_mask.shape[-2:]) != (H, W):
+            raise ValueError(f"meta_forward: q_rgb {tuple(q_rgb.shape)} / s_mask {tuple(s_mask.shape)} do not match "
+                             f"{B} episodes of {H} x {W} images")
+        if q_gt is not None and tuple(q_gt.shape) != (B, H, W):
+            raise ValueError(f"meta_forward: q_gt {tuple(q_gt.shape)} is not [{B}, {H}, {W}]")
+        all_rgb = torch.cat([s_rgb.reshape(B * S, -1, H, W), q_rgb.reshape(B, -1, H, W)], 0)
+        all_x = torch.cat([s_depth.reshape(B * S, *s_depth.shape[2:]), q_depth.reshape(B, *q_depth.shape[1:])], 0)
+        feats = self.encode(all_rgb, all_x)
+        K.TAG = "fss"
+        hs, ws = feats[-1].shape[-2:]
+        foot, count = K.fss_mask_footprint(s_mask.reshape(B * S, H, W).long().contiguous(), (hs, ws))
+        q3, prob, proto = FssProtoSimFn.apply(feats[-1], foot, count, B, S, temperature)
+        K.TAG = "decoder"
+        low = self.decode_head.forward([x[B * S:] for x in feats[:-1]] + [q3])
+        rows, (_, h, w) = _nhwc_rows(low)
+        K.TAG = "fss"
+        if self.keep_episode:
+            self.last_episode = dict(proto=proto.detach(), prob=prob.detach().view(B, hs, ws, 2), foot=foot, count=count)
+
+        def fused():
+            out = K.fss_fuse(rows.detach(), B, h, w, prob.detach(), hs, ws, (H, W), alpha)
+            return out.view(B, H, W, 2).permute(0, 3, 1, 2)
+
+        if q_gt is None:
+            return fused()
+        loss = FssLossFn.apply(rows, prob, B, h, w, hs, ws, q_gt.long(), alpha)
+        return loss, (fused() if self.return_logits else low)

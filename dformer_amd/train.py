@@ -530,6 +530,17 @@ def train_step(model, opt, rgb, depth, label, lr=None):
     """One reference training iteration (train.py:318-357): forward + loss, backward (bucketed
     RCCL all-reduce overlapping it), loss all-reduce, AdamW step. Returns the (device) mean loss."""
     loss, _ = model(rgb, depth, label)
+    return _backward_and_step(loss, opt, lr)
+
+
+def meta_train_step(model, opt, s_rgb, s_depth, s_gt, q_rgb, q_depth, q_gt, lr=None):
+    """One few-shot training iteration (utils/train_trav_fss_v1.py:253-290): the episode loss of
+    model.meta_forward, then the backward, all-reduces and AdamW step of train_step. Eager only."""
+    loss, _ = model.meta_forward(s_rgb, s_depth, s_gt, q_rgb, q_depth, q_gt)
+    return _backward_and_step(loss, opt, lr)
+
+
+def _backward_and_step(loss, opt, lr):
     reduce_loss = all_reduce_mean(loss.detach(), opt.world)
     opt.buckets.main_stream = torch.cuda.current_stream() if loss.is_cuda else None
     if opt.scaler is not None:  # scaler.scale(loss).backward(), the scale read on the device

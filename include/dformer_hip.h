@@ -579,6 +579,63 @@ int dfm_seg_loss_fwd_grad(int dtype, int B, int h, int w, int ncls, const void* 
 int dfm_seg_loss_bwd_gather(int dtype_out, int B, int h, int w, int ncls, const float* grad_partials,
                             const float* loss_out, const float* gscale, void* dlogits, dfm_stream_t stream);
 
+/* ---------------------------------------------------------------- few-shot episodes (meta_forward)
+ * models/builder.py:237-320 collapsed onto stage-3 sized tensors: bilinear upsampling is
+ * linear, so nothing of size C x H x W is formed. Two classes throughout, [bg, fg] (builder.py:296); 255 is
+ * the ignore label (builder.py:307). (hs, ws) is the stage-3 grid h' x w', (h, w) the decode head's; both
+ * upsample to (H, W) with align_corners=False, any factor (hs <= H, ws <= W <= 12288). Caller-owned memory,
+ * no allocation, no synchronisation, float32 accumulation, fixed summation orders and no float atomics: a
+ * second run is bit-identical. New symbols only: dfm_abi_version() stays 13.
+ * mask_footprint (replaces 279-280 and the upsample + mask product of 313-315): mask [n][H][W] int64 ->
+ *   foot[n][k][cell] = sum_p [mask[n](p) == k] * tap(p, cell)  (the adjoint of the upsample applied to the
+ *   class indicator, A_y^T M A_x as an x-pass and a y-pass), count[n][k] = the number of pixels == k (exact;
+ *   H * W < 2^24). Values other than 0 / 1 are in neither class. No gradient. Workspace:
+ *   dfm_fss_footprint_workspace bytes.
+ * proto_pool_fwd (replaces 281-288 and 315-316): f [B*S*cells][ldf] support rows (dtype) ->
+ *   wgt[n*cells + cell][k] = foot[n][k][cell] / ((count[n][k] + 1e-5) * S)  (float32, kept for the backward),
+ *   proto[b][k][:] = sum over the S * cells rows of episode b of wgt[.][k] * f[.][:]  (float32 [B][2][C]).
+ * proto_pool_bwd: df[r][:] = wgt[r][0] * dproto[b][0][:] + wgt[r][1] * dproto[b][1][:]  (dtype).
+ * sim_fwd (replaces 294-297, 319-320): q [B*cells][ldq] query rows (dtype), proto [B][2][C] ->
+ *   cos[r][k] = q_r . P_k / (max(|q_r|, 1e-8) * max(|P_k|, 1e-8))  (a zero prototype gives exactly 0),
+ *   prob[r][:] = softmax_k(20 * cos[r][k] * inv_t); pnorm [B][2] and, unless both NULL (inference), cos
+ *   [rows][2] and qnorm [rows] (the clamped norms) are kept for the backward.
+ * sim_bwd: from dprob [rows][2] writes dq (dtype; += when accumulate: the stage-3 query rows also carry the
+ *   decode head's gradient) and dproto [B][2][C] (summed over the rows of image b in 16 ascending chunks
+ *   combined in ascending order). A clamped norm is a constant. Workspace: dfm_fss_sim_bwd_workspace bytes.
+ * loss_fwd (replaces 298-308): per label pixel z = alpha * up(low) + (1 - alpha) * up(prob) (low
+ *   [B*h*w][ldl] dtype, prob [B*hs*ws][2] float32), two-class CE over the pixels labelled 0 or 1;
+ *   loss_out = (sum, count) as dfm_seg_loss_fwd. gplane (float32 [B][H][W], NULL without a backward)
+ *   receives softmax_1 - [label == 1], 0 on an ignored pixel: with two classes the residual of class 0 is
+ *   its negative. Workspace: dfm_fss_loss_workspace bytes.
+ * loss_bwd: dlow [B*h*w][2] (dtype_out) = alpha * s * up^T(-g, g), dprob [B*hs*ws][2] float32 =
+ *   (1 - alpha) * s * up^T(-g, g), s = gscale / max(count, 1) (gscale: device scalar or NULL = 1): the
+ *   footprint's x-pass / y-pass pair once per grid. Workspace: dfm_fss_loss_bwd_workspace bytes.
+ * fuse_fwd (298-303, eval): out [B*H*W][2] float32 = the fused logits themselves. */
+size_t dfm_fss_footprint_workspace(int n, int hs, int ws, int H, int W); /* 0: unsupported shape */
+int dfm_fss_mask_footprint(int n, int hs, int ws, int H, int W, const long long* mask, float* foot, float* count,
+                           void* workspace, dfm_stream_t stream);
+int dfm_fss_proto_pool_fwd(int dtype, int B, int S, int cells, int C, const void* f, long ldf, const float* foot,
+                           const float* count, float* wgt, float* proto, dfm_stream_t stream);
+int dfm_fss_proto_pool_bwd(int dtype, int B, int S, int cells, int C, const float* wgt, const float* dproto,
+                           void* df, long lddf, dfm_stream_t stream);
+int dfm_fss_sim_fwd(int dtype, int B, int cells, int C, const void* q, long ldq, const float* proto, float inv_t,
+                    float* prob, float* cosv, float* qnorm, float* pnorm, dfm_stream_t stream);
+size_t dfm_fss_sim_bwd_workspace(int B, int cells);
+int dfm_fss_sim_bwd(int dtype, int B, int cells, int C, const void* q, long ldq, const float* proto, float inv_t,
+                    const float* dprob, const float* prob, const float* cosv, const float* qnorm,
+                    const float* pnorm, void* dq, long lddq, int accumulate, float* dproto, void* workspace,
+                    dfm_stream_t stream);
+size_t dfm_fss_loss_workspace(void);
+int dfm_fss_loss_fwd(int dtype, int B, int h, int w, const void* low, long ldl, int hs, int ws, const float* prob,
+                     int H, int W, const long long* label, float alpha, float* gplane, float* loss_out,
+                     void* workspace, dfm_stream_t stream);
+size_t dfm_fss_loss_bwd_workspace(int B, int h, int w, int hs, int ws, int H, int W); /* 0: unsupported shape */
+int dfm_fss_loss_bwd(int dtype_out, int B, int h, int w, int hs, int ws, int H, int W, const float* gplane,
+                     const float* loss_out, const float* gscale, float alpha, void* dlow, float* dprob,
+                     void* workspace, dfm_stream_t stream);
+int dfm_fss_fuse_fwd(int dtype, int B, int h, int w, const void* low, long ldl, int hs, int ws, const float* prob,
+                     int H, int W, float alpha, float* out, dfm_stream_t stream);
+
 /* ---------------------------------------------------------------- optimizer
  * torch.optim.AdamW step (train.py:210-216) over a flat float32 parameter buffer; optional
  * 16-bit shadow copy (copy_dtype DFM_BF16 / DFM_F16) for the next step's GEMM operands.
