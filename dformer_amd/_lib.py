@@ -96,6 +96,10 @@ _SIGS = {
                                       P]),
     "dfm_dwconv_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P, c_int, P, c_long,
                                c_int, P, P, P, P, P]),
+    "dfm_ffn_dgrad_dw3_supported": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dfm_ffn_dgrad_dw3_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dfm_ffn_dgrad_dw3_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P, c_long, P,
+                                      c_long, P, c_int, P, c_long, P, P, P, P, P]),
     "dfm_partial_sum_group": (c_int, [c_int, P, P]),
     "dfm_convffn_supported": (c_int, [c_int, ctypes.POINTER(ConvFFNDesc)]),
     "dfm_convffn_fwd": (c_int, [c_int, ctypes.POINTER(ConvFFNDesc)] + [P] * 20),

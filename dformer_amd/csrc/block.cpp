@@ -232,19 +232,32 @@ void ffn_chain_fwd(Run& r, Shape sh, int C, int R, float eps, V x, const float* 
   linear(r, sv.g, P, R, w2, C, b2, out, e);
 }
 
+constexpr long kFfnDgradDw3MinRows = 65536;  // functional.FFN_DGRAD_DW3_MIN_ROWS
+
 void ffn_chain_bwd(Run& r, Shape sh, int C, int R, V dout, V x, const FfnSaved& sv, const float* ln_w, const void* w1,
                    const float* wpos, const void* w2, const float* ls, const float* rowscale, V dx, const FfnGrads& gr) {
   const long P = sh.P();
   V df = r.temp(P, C);
   residual_bwd(r, P, C, dout, sv.f, ls, rowscale, (long)sh.H * sh.W, df, gr.dls);
   wgrad(r, df, P, C, sv.g, R, gr.dw2, gr.db2);
-  V dhpre = r.temp(P, R);
-  dgrad(r, df, P, C, w2, R, dhpre, false, sv.gp);  // GELU backward: times the stored GELU'(hpre)
-  V dh = r.temp(P, R);
-  void* ws = r.scr(dfm_dwconv_bwd_weight_workspace(sh.B, sh.H, sh.W, R, 3));
-  if (r.live())
-    r.ok(dfm_dwconv_bwd(r.dt, sh.B, sh.H, sh.W, R, 3, sv.h.p, sv.h.ld, dhpre.p, dhpre.ld, wpos, 1, dh.p, dh.ld, 0,
-                        gr.dwpos, gr.dbpos, ws, nullptr, r.s));
+  V dh;
+  // functional.ConvFFNFn's routing rule (FFN_DGRAD_DW3_MIN_ROWS): from 65,536 rows the fc2 input gradient times
+  // the stored GELU'(hpre) runs inside the 3x3 backward and dhpre is never written (nor planned)
+  if (P >= kFfnDgradDw3MinRows && dfm_ffn_dgrad_dw3_supported(r.dt, sh.B, sh.H, sh.W, C, R)) {
+    dh = r.temp(P, R);
+    void* ws = r.scr(dfm_ffn_dgrad_dw3_workspace(sh.B, sh.H, sh.W, R));
+    if (r.live())
+      r.ok(dfm_ffn_dgrad_dw3_bwd(r.dt, sh.B, sh.H, sh.W, C, R, df.p, df.ld, w2, R, sv.gp.p, sv.gp.ld, sv.h.p, sv.h.ld,
+                                 wpos, 1, dh.p, dh.ld, gr.dwpos, gr.dbpos, ws, nullptr, r.s));
+  } else {
+    V dhpre = r.temp(P, R);
+    dgrad(r, df, P, C, w2, R, dhpre, false, sv.gp);  // GELU backward: times the stored GELU'(hpre)
+    dh = r.temp(P, R);
+    void* ws = r.scr(dfm_dwconv_bwd_weight_workspace(sh.B, sh.H, sh.W, R, 3));
+    if (r.live())
+      r.ok(dfm_dwconv_bwd(r.dt, sh.B, sh.H, sh.W, R, 3, sv.h.p, sv.h.ld, dhpre.p, dhpre.ld, wpos, 1, dh.p, dh.ld, 0,
+                          gr.dwpos, gr.dbpos, ws, nullptr, r.s));
+  }
   wgrad(r, dh, P, R, sv.xn, C, gr.dw1, gr.db1);
   V dxn = r.temp(P, C);
   dgrad(r, dh, P, R, w1, C, dxn);

@@ -212,6 +212,15 @@ template <> DFM_INLINE float4_t mma16<f16_t>(bf16x8_t a, bf16x8_t b, float4_t c)
 template <typename T> DFM_INLINE uint16_t bits16(float v);
 template <> DFM_INLINE uint16_t bits16<bf16_t>(float v) { return f2bf(v); }
 template <> DFM_INLINE uint16_t bits16<f16_t>(float v) { return f2h(v); }
+// A wave's own LDS write -> read-back ordering (wave-private staging tiles: no block barrier needed)
+DFM_INLINE void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// 4 consecutive 16-bit elements (8 bytes) from floats
+template <typename T> DFM_INLINE uint2 wide_pack4(const float* v) {
+  const uint32_t w0 = (uint32_t)bits16<T>(v[0]) | ((uint32_t)bits16<T>(v[1]) << 16);
+  const uint32_t w1 = (uint32_t)bits16<T>(v[2]) | ((uint32_t)bits16<T>(v[3]) << 16);
+  return make_uint2(w0, w1);
+}
+template <typename T> DFM_INLINE void wide_st4(T* p, const float* v) { *reinterpret_cast<uint2*>(p) = wide_pack4<T>(v); }
 // 8 floats -> 8 x 16-bit fragment of T (round to nearest even)
 template <typename T> DFM_INLINE bf16x8_t pack16x8(const float* v);
 template <> DFM_INLINE bf16x8_t pack16x8<bf16_t>(const float* v) {

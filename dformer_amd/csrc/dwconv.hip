@@ -1224,7 +1224,7 @@ __global__ __launch_bounds__(256) void dw3_stream_bwd_kernel(int B, int H, int W
 // steps) for the weight gradient. The gather form above re-unpacks its three-row windows for every
 // output row (3x the unpack work, ~1.3 unpack / address instructions per packed FMA); here a step is
 // 72 packed FMAs against 12 loads and 12 unpacks. Pending rows rotate with period 3; the loop is
-// unrolled by 3 so the rotation is register renaming, not moves. 135 VGPRs (the 8-byte-lane kernel:
+// unrolled by 3 so the rotation is register renaming, not moves. 137 VGPRs (the 8-byte-lane kernel:
 // 250), so 3 waves per SIMD. Units are wave-uniform (whole 64-lane channel slices), so the row / column
 // bookkeeping is scalar. Isolated (tools/ffn_kernels_bench.py, DFormer-B bs 16): s0 234 vs 244 us, s1
 // 135 vs 138, s2 34.2 vs 39.2, s3 25.9 vs 30.2 (mlp; mlp_e2 alike); step 480.4 / 482.0 vs 476.5 / 477.1.
@@ -1246,6 +1246,108 @@ template <typename P>
 DFM_INLINE P w3p_zero() {
   if constexpr (sizeof(P) == 4) return 0u;
   else return make_uint2(0u, 0u);
+}
+
+// The row-scatter step's arithmetic, shared by dw3_rows_bwd_kernel and ffn_dgrad_dw3_kernel (which differ
+// in where the dy row comes from). Step r with k = (r - h0 + 1) % 3: dv is the unpacked dy row r, xv the x
+// row r - 1 (out-of-image entries zero), O the three pending input-gradient rows, Cc the unpacked dy centre
+// columns of rows r - 2 .. r, acc the 9 tap + bias partials; in_chunk: dy row r carries the weight gradient.
+// Afterwards O[(k + 2) % 3] is the complete input-gradient row r - 1.
+template <int k, int TW>
+DFM_INLINE void w3r_scatter(const f2v (&wf)[9], const f2v (&dv)[TW + 2], const f2v (&xv)[TW + 2], f2v (&O)[3][TW],
+                            f2v (&Cc)[3][TW], f2v (&acc)[10], bool in_chunk) {
+  constexpr int k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+  // dy row r feeds input-gradient rows r - 1 (taps a = 2), r (a = 1), r + 1 (a = 0, the row's first)
+#pragma unroll
+  for (int t = 0; t < TW; ++t) {
+    O[k1][t] = wf[0] * dv[t];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      O[k2][t] = __builtin_elementwise_fma(wf[6 + j], dv[t + j], O[k2][t]);
+      O[k][t] = __builtin_elementwise_fma(wf[3 + j], dv[t + j], O[k][t]);
+      if (j) O[k1][t] = __builtin_elementwise_fma(wf[j], dv[t + j], O[k1][t]);
+    }
+  }
+  if (in_chunk) {  // dy rows of this chunk carry the weight gradient
+#pragma unroll
+    for (int t = 0; t < TW; ++t) {
+      Cc[k][t] = dv[t + 1];
+      acc[9] += dv[t + 1];
+    }
+  } else {
+#pragma unroll
+    for (int t = 0; t < TW; ++t) Cc[k][t] = f2v{0.f, 0.f};
+  }
+  // x row r - 1 against dy rows r (a = 0), r - 1 (a = 1), r - 2 (a = 2)
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int cr = a == 0 ? k : (a == 1 ? k2 : k1);
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+      for (int t = 0; t < TW; ++t) acc[a * 3 + j] = __builtin_elementwise_fma(Cc[cr][t], xv[t + j], acc[a * 3 + j]);
+  }
+}
+
+// a complete input-gradient row to dx: dp = the strip's first pixel of the row, ncols in-image columns
+template <typename T, int TW>
+DFM_INLINE void w3r_store_row(char* dp, long pix_bytes, unsigned c0b, int ncols, const f2v (&o)[TW], int accumulate) {
+  using P = typename W3Pair<T>::type;
+#pragma unroll
+  for (int t = 0; t < TW; ++t) {
+    if (t >= ncols) break;
+    P* op = reinterpret_cast<P*>(dp + t * pix_bytes + c0b);
+    f2v v = o[t];
+    if (accumulate) v += w3p_unpack<T>(*op);
+    *op = w3p_pack<T>(v);
+  }
+}
+
+// One packed row of a unit's NX-column window: row h of the image at `im` (W pixels of ld_bytes), window column q
+// at byte offset col[q] (+ the lane's c0b); a row outside the image reads row hfb instead and returns false
+template <typename P, int NX>
+DFM_INLINE bool w3r_fetch(const char* im, int W, long ld_bytes, const long (&col)[NX], unsigned c0b, int h, int H,
+                          int hfb, P (&r)[NX]) {
+  const bool ok = h >= 0 && h < H;
+  const char* rp = im + (long)(ok ? h : hfb) * W * ld_bytes;
+#pragma unroll
+  for (int q = 0; q < NX; ++q) r[q] = *reinterpret_cast<const P*>(rp + col[q] + c0b);
+  return ok;
+}
+// ... unpacked, zero where the row (ok) or the column (bit q of cm) is outside the image
+template <typename T, int NX>
+DFM_INLINE void w3r_unpack_row(const typename W3Pair<T>::type (&r)[NX], bool ok, unsigned cm, f2v (&v)[NX]) {
+  if (ok && cm == (1u << NX) - 1) {
+#pragma unroll
+    for (int q = 0; q < NX; ++q) v[q] = w3p_unpack<T>(r[q]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < NX; ++q) v[q] = (ok && ((cm >> q) & 1u)) ? w3p_unpack<T>(r[q]) : f2v{0.f, 0.f};
+  }
+}
+
+// the flipped taps of a lane's channel pair (input gradient), centre tap + 1 when add_identity
+DFM_INLINE void w3r_taps(const float* __restrict__ w, int c0, int add_identity, f2v (&wf)[9]) {
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) {
+    const float idt = (tap == 4 && add_identity) ? 1.0f : 0.0f;
+    wf[tap] = f2v{w[(long)c0 * 9 + 8 - tap] + idt, w[(long)(c0 + 1) * 9 + 8 - tap] + idt};
+  }
+}
+
+// block reduction of the tap / bias partials over the 4 waves -> part[blockIdx.x][C][10] (fixed order)
+DFM_INLINE void w3r_reduce(float (*red)[20][64], const f2v (&acc)[10], int wave, int lane, int ch0, int C,
+                           float* __restrict__ part) {
+  constexpr int NV = 20;
+  const long pbase = (long)blockIdx.x * C * 10;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) red[wave][v][lane] = (v & 1) ? acc[v >> 1].y : acc[v >> 1].x;
+  __syncthreads();
+  for (int idx = threadIdx.x; idx < NV * 64; idx += 256) {
+    const int v = idx / 64, l = idx % 64;
+    const int c = ch0 + l * 2 + (v & 1);
+    if (c < C) part[pbase + (long)c * 10 + (v >> 1)] = red[0][v][l] + red[1][v][l] + red[2][v][l] + red[3][v][l];
+  }
 }
 
 template <typename T>
@@ -1329,42 +1431,13 @@ __global__ __launch_bounds__(256, 3) void dw3_rows_bwd_kernel(int B, int H, int 
     // step r (k = (r - h0 + 1) % 3): D holds dy row r, X x row r - 1; fetches dy row r + 1 and x row r.
     // Rows past h1 + 1 / h1 are never used for anything that is kept.
     auto step = [&](auto kc) {
-      constexpr int k = decltype(kc)::value, k1 = (k + 1) % 3, k2 = (k + 2) % 3;
+      constexpr int k = decltype(kc)::value, k2 = (k + 2) % 3;
       f2v dv[NX], xv[NX];
       unpack_row(D, dok, dv);
       dok = fetch(yim, lddy, ycol, r + 1, D);
       unpack_row(X, xok, xv);
       xok = fetch(xim, ldx, xcol, r, X);
-      // dy row r feeds input-gradient rows r - 1 (taps a = 2), r (a = 1), r + 1 (a = 0, the row's first)
-#pragma unroll
-      for (int t = 0; t < TW; ++t) {
-        O[k1][t] = wf[0] * dv[t];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-          O[k2][t] = __builtin_elementwise_fma(wf[6 + j], dv[t + j], O[k2][t]);
-          O[k][t] = __builtin_elementwise_fma(wf[3 + j], dv[t + j], O[k][t]);
-          if (j) O[k1][t] = __builtin_elementwise_fma(wf[j], dv[t + j], O[k1][t]);
-        }
-      }
-      if (r >= h0 && r < h1) {  // dy rows of this chunk carry the weight gradient
-#pragma unroll
-        for (int t = 0; t < TW; ++t) {
-          Cc[k][t] = dv[t + 1];
-          acc[9] += dv[t + 1];
-        }
-      } else {
-#pragma unroll
-        for (int t = 0; t < TW; ++t) Cc[k][t] = f2v{0.f, 0.f};
-      }
-      // x row r - 1 against dy rows r (a = 0), r - 1 (a = 1), r - 2 (a = 2)
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const int cr = a == 0 ? k : (a == 1 ? k2 : k1);
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-          for (int t = 0; t < TW; ++t) acc[a * 3 + j] = __builtin_elementwise_fma(Cc[cr][t], xv[t + j], acc[a * 3 + j]);
-      }
+      w3r_scatter<k, TW>(wf, dv, xv, O, Cc, acc, r >= h0 && r < h1);
       // input-gradient row r - 1 is complete
       if (r - 1 >= h0 && r - 1 < h1 && cvalid) {
         char* dp = reinterpret_cast<char*>(dx + ((b * H + r - 1) * W + w0) * lddx);
@@ -1400,7 +1473,7 @@ __global__ __launch_bounds__(256, 3) void dw3_rows_bwd_kernel(int B, int H, int 
   }
 }
 
-// waves per SIMD of dw3_rows_bwd_kernel (135 VGPRs; its geometry's round size). Capped at 4 (128 VGPRs)
+// waves per SIMD of dw3_rows_bwd_kernel (137 VGPRs; its geometry's round size). Capped at 4 (128 VGPRs)
 // it spills and is 10-22 % slower (s0 286 vs 234 us; step 470.2 vs 480.8 images/s)
 constexpr int W3R_WPS = 3;
 
@@ -1424,6 +1497,273 @@ long b3_launch(int B, int H, int W, int C, const void* x, long ldx, const void* 
                      g.RC, g.nstrips, g.nchunks, g.LPU, g.UPW, (const T*)x, ldx, (const T*)dy, lddy, w, id,
                      (T*)dx, lddx, acc, part);
   return g.nsb;
+}
+
+// ---------------------------------------------------------------- fc2 input gradient x GELU' inside the 3x3 backward
+// The op-level ConvFFN backward's pair  dhpre = (df @ W2) * gp  (gemm_wide_kernel: reads gp, WRITES dhpre) and
+// dw3_rows_bwd_kernel (READS dhpre, h; writes dh) as one kernel that keeps dhpre on chip: 2 of the pair's 5
+// passes over a [P][hidden] tensor (315 MB at stage 0) and one launch go away. Both halves are the pair's:
+//   front end (gemm_wide_kernel's data path): the block's 128-column W2 slice stays in LDS as [n][k]; a wave
+//     loads the df fragments of 16 pixels straight from global memory, multiplies (W as the MFMA A operand: a
+//     lane holds 4 channels of one pixel), takes the GELU' rows in as coalesced 16-byte rows through its tile
+//     of the ring and rounds the product to the 16-bit dtype, exactly where the pair rounds dhpre;
+//   hand-off: the tile stays in LDS: the ring holds FD_G = 3 image rows of the block's strip (FD_SW = 16 output
+//     columns + 2 halo columns = 18 pixels x 128 channels per row; 54 of the 64 pixels the four waves' tiles
+//     cover), which is the transposition from the MFMA layout to the row-scatter layout (a lane owns one
+//     channel pair of every pixel);
+//   back end (dw3_rows_bwd_kernel's step, w3r_scatter): wave i owns columns 4 i .. 4 i + 3 of the strip and
+//     takes its dy rows from the ring, its h rows from global memory one step ahead, as there.
+// A unit is (image, row chunk, 16-column strip) of the block's 128-channel slice (blockIdx.y), block-uniform;
+// a block walks units blockIdx.x, + gridDim.x, ... Three rows per ring fill is the row-scatter's rotation
+// period, so a fill is followed by steps k = 0, 1, 2. dhpre of out-of-image pixels is zero; in-image halo
+// pixels are recomputed (2 of 18 columns, 2 rows per chunk: neighbouring units run side by side, so their gp /
+// df lines come from L2). The operands of the next fill (the next unit's first, at a unit's end) are loaded
+// into registers before the three steps, so their latency hides under the steps' FMAs. Two block barriers
+// per fill (ring free / ring complete, LDS-only waits); no communication between blocks, no atomics: the
+// per-block partials go to part[blockIdx.x][hidden][10] in fixed order, as dw3_rows_bwd_kernel's.
+// LDS: W2 slice 128 x (K + 8) x 2 B + ring 64 x 136 x 2 B = 27.6 / 35.8 / 52.2 KB at K = 32 / 64 / 128
+// (the reduction buffer aliases them), so three blocks share a CU at every K.
+constexpr int FD_SW = 4 * W3_TW;      // output columns of a block's strip
+constexpr int FD_RW = FD_SW + 2;      // ring columns: the strip and its halo
+constexpr int FD_G = 3;               // image rows per ring fill
+constexpr int FD_NSL = 128;           // channels per block
+constexpr int FD_SP = FD_NSL + 8;     // ring pixel pitch (elements): conflict-free 8-byte accumulator-layout accesses
+constexpr int FD_BPC = 3;             // blocks per CU (launch bounds; 168 VGPRs)
+static_assert(FD_G * FD_RW <= 64, "a ring fill is one 16-pixel MFMA tile per wave");
+
+template <int KD>
+struct FdCfg {
+  static constexpr int WP = KD + 8;  // W image pitch (elements): conflict-free b128 fragments
+  static constexpr int W_BYTES = FD_NSL * WP * 2;
+  static constexpr int RING_BYTES = 64 * FD_SP * 2;
+  static constexpr int LDS = W_BYTES + RING_BYTES;
+  static_assert(LDS >= 4 * 20 * 64 * 4, "the reduction buffer aliases the W slice and the ring");
+};
+
+struct FdGeom {
+  int RC, nstrips, nchunks, slices;
+  long units, nsb;
+};
+// Row chunks: a launch runs in rounds of 256 CUs x FD_BPC blocks; the chunk count minimises rounds x ring
+// fills per unit (a unit of rc rows takes rc + 3 steps), chunks of at least 5 rows (w3_geom_cpl's rule)
+inline FdGeom fd_geom(int B, int H, int W, int hidden) {
+  FdGeom g;
+  g.slices = hidden / FD_NSL;
+  g.nstrips = (W + FD_SW - 1) / FD_SW;
+  const long slots = 256L * FD_BPC;
+  const int max_chunks = std::max(1, H / 5);
+  long best = -1;
+  g.RC = H;
+  for (int n = 1; n <= max_chunks; ++n) {
+    const int rc = (H + n - 1) / n;
+    if (n > 1 && (H + rc - 1) / rc != n) continue;  // same row chunk as a smaller count
+    const long blocks = w3_units(B, g.nstrips, n) * g.slices;
+    const long cost = (blocks + slots - 1) / slots * ((rc + 3 + FD_G - 1) / FD_G);
+    if (best < 0 || cost < best) {
+      best = cost;
+      g.RC = rc;
+    }
+  }
+  g.nchunks = (H + g.RC - 1) / g.RC;
+  g.units = w3_units(B, g.nstrips, g.nchunks);
+  g.nsb = std::max(1L, std::min(g.units, std::max(1L, slots / g.slices)));
+  return g;
+}
+
+// Front-end operands of ring fill gi of unit u, into registers (see ffn_dgrad_dw3_kernel)
+typedef uint32_t fd_u32x4 __attribute__((ext_vector_type(4)));  // 16 bytes as a native vector (stays in registers)
+template <typename T>
+struct FdArgs {
+  const T *df, *gp;
+  long lddf, ldgp, upi;
+  int H, W, RC, nstrips, nchunks, n0, wave, lane;
+};
+template <typename T>
+DFM_INLINE long fd_pixel(const FdArgs<T>& a, long b, int rbase, int w0, int h0, int h1, int i, bool& ok) {
+  const int rr = i / FD_RW, cc = i - rr * FD_RW;
+  const int r = rbase + rr, c = w0 - 1 + cc;
+  ok = i < FD_G * FD_RW && r >= 0 && r < a.H && r <= h1 && c >= 0 && c < a.W;
+  return (b * a.H + (ok ? r : h0)) * a.W + (ok ? c : w0);
+}
+template <typename T, int KS, bool LOAD_A, bool LOAD_E>
+DFM_INLINE void fd_issue(const FdArgs<T>& a, long u, int gi, bf16x8_t (&af)[KS], fd_u32x4 (&ev)[4], bool& fval) {
+  const int strip = (int)(u % a.nstrips), chunk = (int)((u / a.nstrips) % a.nchunks);
+  const long b = u / a.upi;
+  const int w0 = strip * FD_SW, h0 = chunk * a.RC, h1 = min(h0 + a.RC, a.H);
+  const int rbase = h0 - 1 + FD_G * gi;
+  const long p = fd_pixel(a, b, rbase, w0, h0, h1, a.wave * 16 + (a.lane & 15), fval);
+  const T* ap = a.df + p * a.lddf + 8 * (a.lane >> 4);
+  if constexpr (LOAD_A) {
+#pragma unroll
+    for (int s = 0; s < KS; ++s) af[s] = *reinterpret_cast<const bf16x8_t*>(ap + 32 * s);
+  }
+  if constexpr (!LOAD_E) return;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int q = i * 64 + a.lane;
+    bool ok;
+    const long pe = fd_pixel(a, b, rbase, w0, h0, h1, a.wave * 16 + (q >> 4), ok);
+    ev[i] = *reinterpret_cast<const fd_u32x4*>(a.gp + pe * a.ldgp + a.n0 + (q & 15) * 8);
+  }
+}
+
+template <typename T, int KD>
+__global__ __launch_bounds__(256, FD_BPC) void ffn_dgrad_dw3_kernel(
+    int B, int H, int W, int hidden, int RC, int nstrips, int nchunks, const T* __restrict__ df, long lddf,
+    const T* __restrict__ w2, long ldw2, const T* __restrict__ gp, long ldgp, const T* __restrict__ x, long ldx,
+    const float* __restrict__ w, int add_identity, T* __restrict__ dx, long lddx, float* __restrict__ part) {
+  using CF = FdCfg<KD>;
+  using P = typename W3Pair<T>::type;
+  constexpr int TW = W3_TW, NX = TW + 2, KS = KD / 32, NT = FD_NSL / 16;
+  constexpr long ES = sizeof(T);
+  // the df fragments are prefetched with the GELU' rows while they fit in the 168 VGPRs of 3 waves per SIMD; at K = 128
+  // (16 more registers) they are loaded at the fill itself: df is re-read by every channel slice, so it comes from L2
+  constexpr bool PFA = KD < 128;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* wimg = reinterpret_cast<bf16_t*>(smem);
+  T* ring = reinterpret_cast<T*>(smem + CF::W_BYTES);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  T* stg = ring + wave * 16 * FD_SP;  // this wave's 16-pixel tile of the ring
+  const int n0 = blockIdx.y * FD_NSL;
+  const int c0 = n0 + 2 * lane;  // the lane's channel pair (hidden % 128 == 0: always in range)
+  const long units = w3_units(B, nstrips, nchunks);
+  const long upi = (long)nstrips * nchunks;
+
+  // ---- the block's W2 slice -> LDS as [n][k]: w2 is [k][n], 16-byte n-vectors transposed into the image
+  for (int e = threadIdx.x; e < KD * (FD_NSL / 8); e += 256) {
+    const int k = e / (FD_NSL / 8), nl = (e % (FD_NSL / 8)) * 8;
+    const uint4 v = *reinterpret_cast<const uint4*>(w2 + (long)k * ldw2 + n0 + nl);
+    const uint16_t* hv = reinterpret_cast<const uint16_t*>(&v);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) reinterpret_cast<uint16_t*>(wimg)[(nl + i) * CF::WP + k] = hv[i];
+  }
+  f2v wf[9];
+  w3r_taps(w, c0, add_identity, wf);
+  f2v acc[10];
+#pragma unroll
+  for (int a = 0; a < 10; ++a) acc[a] = f2v{0.f, 0.f};
+  const unsigned c0b = (unsigned)(c0 * ES);
+  __syncthreads();
+
+  // ---- front-end operands of ring fill gi of unit u, into registers: the df fragments of this lane's pixel
+  // (MFMA B operand: pixel lane & 15 of the wave's tile, k-vector lane >> 4) and four 16-byte pieces of the
+  // tile's GELU' rows. Ring pixel i of a fill is row i / 18, column i % 18 of the 3 x 18 window; a pixel
+  // outside the image, past the chunk's lower halo row or past the window reads the unit's first pixel
+  // (in the image) and its product is zeroed (fval).
+  bf16x8_t af[KS];
+  fd_u32x4 ev[4];
+  bool fval = false;
+  const FdArgs<T> fa{df, gp, lddf, ldgp, upi, H, W, RC, nstrips, nchunks, n0, wave, lane};
+
+  long u = blockIdx.x;
+  if (u < units) fd_issue<T, KS, PFA, true>(fa, u, 0, af, ev, fval);
+  for (; u < units; u += gridDim.x) {
+    const int strip = (int)(u % nstrips), chunk = (int)((u / nstrips) % nchunks);
+    const long b = u / upi;
+    const int w0 = strip * FD_SW + wave * TW;  // this wave's columns of the block's strip
+    const int h0 = chunk * RC, h1 = min(h0 + RC, H);
+    const bool active = w0 < W;  // (wave-uniform) a wave past the image's right edge only fills its ring tile
+    const int nfills = (h1 - h0 + 3 + FD_G - 1) / FD_G;
+    unsigned cm = 0;  // in-image window columns (out-of-image ones read column w0 and are zeroed)
+    long xcol[NX];
+#pragma unroll
+    for (int q = 0; q < NX; ++q) {
+      const bool in = w0 - 1 + q >= 0 && w0 - 1 + q < W;
+      cm |= (unsigned)in << q;
+      xcol[q] = (in ? w0 - 1 + q : w0) * ldx * ES;
+    }
+    const char* xim = reinterpret_cast<const char*>(x + b * H * W * ldx);
+    P X[NX];
+    bool xok = false;
+    f2v O[3][TW], Cc[3][TW];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int t = 0; t < TW; ++t) O[i][t] = Cc[i][t] = f2v{0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < NX; ++q) X[q] = w3p_zero<P>();
+    int r = h0 - 1;
+    // step r (k = (r - h0 + 1) % 3 = its row of the ring): dy row r from the ring, X holds x row r - 1;
+    // fetches x row r
+    auto step = [&](auto kc) {
+      constexpr int k = decltype(kc)::value;
+      f2v dv[NX], xv[NX];
+      const T* rp = ring + (k * FD_RW + wave * TW) * FD_SP + 2 * lane;
+#pragma unroll
+      for (int q = 0; q < NX; ++q) dv[q] = w3p_unpack<T>(*reinterpret_cast<const P*>(rp + q * FD_SP));
+      w3r_unpack_row<T>(X, xok, cm, xv);
+      xok = w3r_fetch(xim, W, ldx * ES, xcol, c0b, r, H, h0, X);
+      w3r_scatter<k, TW>(wf, dv, xv, O, Cc, acc, r >= h0 && r < h1);
+      if (r - 1 >= h0 && r - 1 < h1)
+        w3r_store_row<T, TW>(reinterpret_cast<char*>(dx + ((b * H + r - 1) * W + w0) * lddx), lddx * ES, c0b, W - w0,
+                             O[(k + 2) % 3], 0);
+    };
+    for (int gi = 0; gi < nfills; ++gi) {
+      if constexpr (!PFA) fd_issue<T, KS, true, false>(fa, u, gi, af, ev, fval);
+      lds_barrier();  // every wave has read the previous fill's rows
+      // ---- front end: GELU' rows into the tile, the products over them (same lane, same address)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int q = i * 64 + lane;
+        *reinterpret_cast<fd_u32x4*>(stg + (q >> 4) * FD_SP + (q & 15) * 8) = ev[i];
+      }
+      wave_lds_fence();
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        float4_t a4 = float4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+          const bf16x8_t wfr = __builtin_bit_cast(
+              bf16x8_t, *reinterpret_cast<const uint4*>(wimg + (t * 16 + (lane & 15)) * CF::WP + 32 * s + 8 * (lane >> 4)));
+          a4 = mma16<T>(wfr, af[s], a4);
+        }
+        T* sp = stg + (lane & 15) * FD_SP + t * 16 + 4 * (lane >> 4);
+        const uint2 eu = *reinterpret_cast<const uint2*>(sp);
+        const T* eh = reinterpret_cast<const T*>(&eu);
+        // rounded to T here as the GEMM's epilogue rounds dhpre: the product in fp32, then the conversion, so dhpre
+        // is bit for bit the pair's (the empty asm keeps the compiler from folding product and rounding
+        // into one mixed-precision instruction, whose single rounding differs on fp16 ties); the
+        // out-of-image zero is selected on the packed words
+        float v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          v[i] = a4[i] * Num<T>::to_f(eh[i]);
+          asm volatile("" : "+v"(v[i]));
+        }
+        const uint2 pk = wide_pack4<T>(v);
+        *reinterpret_cast<uint2*>(sp) = fval ? pk : make_uint2(0u, 0u);
+      }
+      // ---- the next fill's operands, in flight during the steps
+      // (unconditional: after the block's last fill it re-reads the unit's first operands, which nobody uses)
+      const bool last = gi + 1 == nfills;
+      fd_issue<T, KS, PFA, true>(fa, last && u + gridDim.x < units ? u + gridDim.x : u, last ? 0 : gi + 1, af, ev, fval);
+      lds_barrier();  // the ring's three rows are complete
+      // ---- back end: three row-scatter steps
+      if (active) {
+        if (r <= h1 + 1) { step(std::integral_constant<int, 0>{}); ++r; }
+        if (r <= h1 + 1) { step(std::integral_constant<int, 1>{}); ++r; }
+        if (r <= h1 + 1) { step(std::integral_constant<int, 2>{}); ++r; }
+      }
+    }
+  }
+
+  __syncthreads();  // the reduction buffer aliases the W slice and the ring
+  w3r_reduce(reinterpret_cast<float(*)[20][64]>(smem), acc, wave, lane, n0, hidden, part);
+}
+
+template <typename T, int KD>
+void fd_launch_k(const FdGeom& g, int B, int H, int W, int hidden, const void* df, long lddf, const void* w2, long ldw2,
+                 const void* gp, long ldgp, const void* x, long ldx, const float* w, int id, void* dx, long lddx,
+                 float* part, hipStream_t s) {
+  DFM_LAUNCH((ffn_dgrad_dw3_kernel<T, KD>), dim3((unsigned)g.nsb, (unsigned)g.slices), dim3(256), FdCfg<KD>::LDS, s, B, H,
+             W, hidden, g.RC, g.nstrips, g.nchunks, (const T*)df, lddf, (const T*)w2, ldw2, (const T*)gp, ldgp,
+             (const T*)x, ldx, w, id, (T*)dx, lddx, part);
+}
+
+inline bool fd_shape_ok(int B, int H, int W, int C, int hidden) {
+  return B > 0 && H > 0 && W > 0 && (C == 32 || C == 64 || C == 128) && hidden >= FD_NSL && hidden % FD_NSL == 0 &&
+         hidden / FD_NSL <= 65535;
 }
 
 template <typename T>
@@ -1540,6 +1880,42 @@ extern "C" int dfm_dwconv_bwd(int dtype, int B, int H, int W, int C, int k, cons
   });
   DFM_LAUNCH_CHECK();
   return second_stage(2, (int)nsb, (long)C * (k * k + 1), part, dw, db, (long)(k * k + 1), 0, defer, s);
+}
+
+extern "C" int dfm_ffn_dgrad_dw3_supported(int dtype, int B, int H, int W, int C, int hidden) {
+  return (dtype == DFM_BF16 || dtype == DFM_F16) && fd_shape_ok(B, H, W, C, hidden);
+}
+
+extern "C" size_t dfm_ffn_dgrad_dw3_workspace(int B, int H, int W, int hidden) {
+  if (B <= 0 || H <= 0 || W <= 0 || hidden < FD_NSL || hidden % FD_NSL != 0) return 0;
+  return (size_t)fd_geom(B, H, W, hidden).nsb * hidden * 10 * sizeof(float);
+}
+
+extern "C" int dfm_ffn_dgrad_dw3_bwd(int dtype, int B, int H, int W, int C, int hidden, const void* df, long lddf,
+                                     const void* w2, long ldw2, const void* gp, long ldgp, const void* h, long ldh,
+                                     const float* wpos, int add_identity, void* dh, long lddh, float* dw, float* db,
+                                     void* workspace, DfmPartialSum* defer, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE16(dtype);
+  if (defer) *defer = DfmPartialSum{};
+  DFM_CHECK_ARG(fd_shape_ok(B, H, W, C, hidden), "dfm_ffn_dgrad_dw3_bwd: shape B=%d H=%d W=%d C=%d hidden=%d unsupported",
+                B, H, W, C, hidden);
+  DFM_CHECK_ARG(df && w2 && gp && h && wpos && dh && dw && workspace, "dfm_ffn_dgrad_dw3_bwd: null argument");
+  auto vec16 = [](const void* p, long ld, int cols) { return ld >= cols && ld % 8 == 0 && ((uintptr_t)p % 16) == 0; };
+  DFM_CHECK_ARG(vec16(df, lddf, C) && vec16(w2, ldw2, hidden) && vec16(gp, ldgp, hidden) && vec16(h, ldh, hidden) &&
+                    vec16(dh, lddh, hidden),
+                "dfm_ffn_dgrad_dw3_bwd: row strides and pointers must be 16-byte vector aligned and cover the row");
+  // 32-bit byte offsets within an image row (the row-scatter loads), element offsets in long everywhere else
+  DFM_CHECK_ARG((long)W * std::max(ldh, lddh) * 2 < (1L << 31), "dfm_ffn_dgrad_dw3_bwd: row of %d pixels too long", W);
+  hipStream_t s = (hipStream_t)stream;
+  float* part = (float*)workspace;
+  const FdGeom g = fd_geom(B, H, W, hidden);
+  DFM_DTYPE_SWITCH16(dtype, T, {
+    if (C == 32) fd_launch_k<T, 32>(g, B, H, W, hidden, df, lddf, w2, ldw2, gp, ldgp, h, ldh, wpos, add_identity, dh, lddh, part, s);
+    else if (C == 64) fd_launch_k<T, 64>(g, B, H, W, hidden, df, lddf, w2, ldw2, gp, ldgp, h, ldh, wpos, add_identity, dh, lddh, part, s);
+    else fd_launch_k<T, 128>(g, B, H, W, hidden, df, lddf, w2, ldw2, gp, ldgp, h, ldh, wpos, add_identity, dh, lddh, part, s);
+  });
+  DFM_LAUNCH_CHECK();
+  return second_stage(2, (int)g.nsb, (long)hidden * 10, part, dw, db, 10L, 0, defer, s);
 }
 
 extern "C" int dfm_dwconv_bwd_weight(int dtype, int B, int H, int W, int C, int k, const void* x, long ldx,

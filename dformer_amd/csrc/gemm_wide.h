@@ -29,15 +29,6 @@ struct WideCfg {
   static constexpr int LDS = W_BYTES + 4 * S_BYTES + 2 * WIDE_NSL * 4;
 };
 
-DFM_INLINE void wave_lds_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// 4 consecutive 16-bit elements (8 bytes) from floats
-template <typename T> DFM_INLINE void wide_st4(T* p, const float* v) {
-  const uint32_t w0 = (uint32_t)bits16<T>(v[0]) | ((uint32_t)bits16<T>(v[1]) << 16);
-  const uint32_t w1 = (uint32_t)bits16<T>(v[2]) | ((uint32_t)bits16<T>(v[3]) << 16);
-  *reinterpret_cast<uint2*>(p) = make_uint2(w0, w1);
-}
-
 // ekind: 0 none, 1 multiplier (GELU' of it with mul_gelu_grad), 2 residual (+ colscale * rowscale *
 // branch), 3 beta * C. ep / lde: that operand.
 template <typename T, int KD, bool BKC>

@@ -178,6 +178,10 @@ def _cat1(*vs):
 # stage 1 on, tools/ffn_kernels_bench.py); False routes every ConvFFN through the op-level chain below
 # (tests compare them; DFM_FUSED_FFN=0|1|fwd|auto sets the default for A/B runs)
 FUSED_FWD_MIN_PLANE = 16384
+# The op-level backward's fc2 input gradient (times the stored GELU') runs inside the 3x3 backward
+# (kernels.ffn_dgrad_dw3_bwd: dhpre is never written) from this many rows, the row count from which the
+# short-K wide GEMM it replaces is routed (stages 0-1 at 480 x 640, batch 16); below it the pair stays.
+FFN_DGRAD_DW3_MIN_ROWS = 65536
 _FUSED_FFN_MODES = {"0": False, "1": True, "fwd": "fwd", "auto": "auto"}
 
 
@@ -255,10 +259,16 @@ class ConvFFNFn(torch.autograd.Function):
             W1, W2 = wcast(dt, w1), wcast(dt, w2)
             df, dls = K.residual_bwd(dout, f, ls, rowscale, H * W)
             dW2, db2 = K.linear_wgrad(df, g, out=gslot2(w2), bias_grad=True, bias_out=gslot(b2))
-            dhpre = K.linear_dgrad(df, W2, mul=gp)  # GELU backward: times the stored GELU'(hpre)
-            # input and weight gradients of DW3x3 + identity in one pass over dhpre, h
-            dh, dwpos, dbpos = K.dwconv_bwd(h, dhpre, ctx.shape, wpos, 3, add_identity=True, dw=gslot(wpos),
-                                            db=gslot(bpos))
+            if h.shape[0] >= FFN_DGRAD_DW3_MIN_ROWS and K.ffn_dgrad_dw3_supported(dt, ctx.shape, df.shape[1], h.shape[1],
+                                                                                  operands=(df, W2, gp, h)):
+                # the fc2 input gradient times the stored GELU' inside the 3x3 backward: dhpre stays on chip
+                dh, dwpos, dbpos = K.ffn_dgrad_dw3_bwd(df, W2, gp, h, ctx.shape, wpos, add_identity=True,
+                                                       dw=gslot(wpos), db=gslot(bpos))
+            else:
+                dhpre = K.linear_dgrad(df, W2, mul=gp)  # GELU backward: times the stored GELU'(hpre)
+                # input and weight gradients of DW3x3 + identity in one pass over dhpre, h
+                dh, dwpos, dbpos = K.dwconv_bwd(h, dhpre, ctx.shape, wpos, 3, add_identity=True, dw=gslot(wpos),
+                                                db=gslot(bpos))
             dW1, db1 = K.linear_wgrad(dh, xn, out=gslot2(w1), bias_grad=True, bias_out=gslot(b1))
             dxn = K.linear_dgrad(dh, W1)
             dx, dlnw, dlnb = K.layernorm_bwd(x, dxn, ln_w, mu, rs, dres=dout)

@@ -521,6 +521,42 @@ def dwconv_bwd(x, dy, shape, w, k, add_identity=False, dx=None, accumulate=False
     return dx, dw, db
 
 
+def ffn_dgrad_dw3_supported(dtype, shape, C, hidden, operands=()):
+    """Whether ffn_dgrad_dw3_bwd takes this dtype and shape and, when given, these operands (df, w2, gp, h, dh):
+    the entry point wants rows of 16-byte vectors (contiguous inner dimension, row stride a multiple of 8
+    elements, 16-byte aligned pointer). A caller that gets False takes the pair."""
+    if dtype not in (torch.bfloat16, torch.float16):
+        return False
+    for t in operands:
+        if t is not None and (t.dim() != 2 or t.stride(1) != 1 or t.stride(0) % 8 or t.data_ptr() % 16):
+            return False
+    B, H, W = shape
+    code = _lib.BF16 if dtype == torch.bfloat16 else _lib.F16
+    return bool(lib.dfm_ffn_dgrad_dw3_supported(code, B, H, W, C, hidden))
+
+
+def ffn_dgrad_dw3_bwd(df, w2, gp, h, shape, wpos, add_identity=True, dh=None, dw=None, db=None):
+    """dh, dwpos, dbpos of hpre = DW3x3(h) + bpos + h for dhpre = (df @ w2) * gp in one kernel: the pair
+    linear_dgrad(df, w2, mul=gp) + dwconv_bwd(h, dhpre, ...) without dhpre in memory (dfm_ffn_dgrad_dw3_bwd).
+    w2: the forward's fc2 weight [C, hidden]. An unsupported shape raises before any launch."""
+    B, H, W = shape
+    P, C = df.shape
+    R = w2.shape[1]
+    if dh is None:
+        dh = torch.empty(P, R, device=df.device, dtype=df.dtype)
+    if dw is None:
+        dw = torch.empty(R, 1, 3, 3, device=df.device, dtype=torch.float32)
+    if db is None:
+        db = torch.empty(R, device=df.device, dtype=torch.float32)
+    ws, ps = _red_ws(lib.dfm_ffn_dgrad_dw3_workspace(B, H, W, R), df.device)
+    check(lib.dfm_ffn_dgrad_dw3_bwd(dtype_code(df), B, H, W, C, R, ptr(df), ld(df), ptr(w2), ld(w2), ptr(gp), ld(gp),
+                                    ptr(h), ld(h), ptr(wpos), int(add_identity), ptr(dh), ld(dh), ptr(dw), ptr(db),
+                                    ptr(ws), _pref(ps), stream()), "dfm_ffn_dgrad_dw3_bwd")
+    if ACCOUNT is not None:
+        _acct(2.0 * P * C * R + 36.0 * P * R, _es(df) * P * (C + 3 * R))
+    return dh, dw, db
+
+
 def dwconv_bwd_weight(x, dy, shape, k, dw=None, db=None):
     B, H, W = shape
     C = x.shape[1]

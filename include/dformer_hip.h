@@ -200,6 +200,21 @@ int dfm_dwconv_bwd_weight(int dtype, int B, int H, int W, int C, int k, const vo
 int dfm_dwconv_bwd(int dtype, int B, int H, int W, int C, int k, const void* x, long ldx, const void* dy,
                    long lddy, const float* w, int add_identity, void* dx, long lddx, int accumulate, float* dw,
                    float* db, void* workspace, DfmPartialSum* defer, dfm_stream_t stream);
+/* The ConvFFN backward's fc2 input gradient fused into the 3x3 backward (ffn_dgrad_dw3_kernel, dwconv.hip):
+ * dh, dwpos, dbpos of  hpre = DW3x3(h) + bpos + h  for  dhpre = (df @ W2) * gp,  dhpre never written (it is
+ * rounded to dtype in the kernel exactly where dfm_gemm would round it, so the results are those of
+ * dfm_gemm(mul = gp) + dfm_dwconv_bwd):
+ * df [P][lddf] (C columns), w2 [C][ldw2] (hidden columns, the forward's fc2 weight as the input-gradient GEMM
+ * takes it), gp, h [P][ld] (hidden columns), dh [P][lddh]; dw [hidden][3][3], db [hidden] overwritten;
+ * workspace from dfm_ffn_dgrad_dw3_workspace; defer as dfm_dwconv_bwd. bf16 / f16, C in {32, 64, 128},
+ * hidden % 128 == 0: dfm_ffn_dgrad_dw3_supported says so; anything else is DFM_ERR_ARG before any launch
+ * (the caller then takes the pair). New symbols only: dfm_abi_version() stays 13. */
+int dfm_ffn_dgrad_dw3_supported(int dtype, int B, int H, int W, int C, int hidden);
+size_t dfm_ffn_dgrad_dw3_workspace(int B, int H, int W, int hidden);
+int dfm_ffn_dgrad_dw3_bwd(int dtype, int B, int H, int W, int C, int hidden, const void* df, long lddf,
+                          const void* w2, long ldw2, const void* gp, long ldgp, const void* h, long ldh,
+                          const float* wpos, int add_identity, void* dh, long lddh, float* dw, float* db,
+                          void* workspace, DfmPartialSum* defer, dfm_stream_t stream);
 
 /* ---------------------------------------------------------------- fused ConvFFN (K4)
  * DFormer.py:48-67 (MLP: LN -> fc1 -> DW3x3 + identity -> GELU -> fc2) inside Block's residual

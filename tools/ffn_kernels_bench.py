@@ -2,7 +2,12 @@
 DFormer-B bf16 bs=16 480x640 stage shapes, against its algorithmic HBM bytes (profiling tool, GPU
 only): which of the memory-bound kernels is furthest from the ~6.3 TB/s a streaming kernel reaches.
 
-    python tools/ffn_kernels_bench.py [stage ...] [--json out.json]
+    python tools/ffn_kernels_bench.py [stage ...] [--json out.json] [--match dgrad,dw3_bwd]
+
+--match times only the rows whose name contains one of the comma-separated substrings (e.g. the fc2 input
+gradient + 3x3 backward pair next to the kernel that fuses them, "FUSED dgrad+dw3").
+Compare rows within one run: a --match run launches less before each timed row and its absolute times read
+up to ~10 % slower than a full run's of the same binary (measured on dw3_bwd at stages 0-1).
 """
 import json
 import os
@@ -39,7 +44,7 @@ def timed(fn, it=20):
     return e0.elapsed_time(e1) * 1e3 / it
 
 
-def bench_stage(st, branch="mlp"):
+def bench_stage(st, branch="mlp", match=None):
     H, W, C, r = STAGES[st]
     if branch == "mlp_e2":
         C //= 2
@@ -95,6 +100,11 @@ def bench_stage(st, branch="mlp"):
                                                   save_gelu=True),
              P * (3 * C + 3 * hid) * E),
         ]
+    if K.ffn_dgrad_dw3_supported(bf, (B, H, W), C, hid):  # the pair fc2_dgrad*gp + dw3_bwd as one kernel
+        rows.append(("FUSED dgrad+dw3", lambda: K.ffn_dgrad_dw3_bwd(df, w2, gp, h, (B, H, W), wpos, dh=dh),
+                     P * (C + 3 * hid) * E))
+    if match:
+        rows = [r for r in rows if any(m in r[0] for m in match)]
     res = []
     for name, fn, nb in rows:
         us = timed(fn)
@@ -114,23 +124,27 @@ def _wg(df, g, dh, xn):
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     out = sys.argv[sys.argv.index("--json") + 1] if "--json" in sys.argv else None
+    match = sys.argv[sys.argv.index("--match") + 1].split(",") if "--match" in sys.argv else None
     stages = [int(a) for a in args if a.isdigit()] or [0, 1, 2]
     allr = []
     for st in stages:
         for br in ("mlp", "mlp_e2"):
-            allr += bench_stage(st, br)
+            allr += bench_stage(st, br, match)
     for st in stages:
         for br in ("mlp", "mlp_e2"):
             rr = [r for r in allr if r["stage"] == st and r["branch"] == br]
             unf = [r["us"] for r in rr if not r["kernel"].startswith("FUSED")]
             fus = {r["kernel"]: r["us"] for r in rr if r["kernel"].startswith("FUSED")}
-            if fus:
+            if "FUSED dgrad+dw3" in fus:
+                pair = sum(r["us"] for r in rr if r["kernel"] in ("fc2_dgrad*gp", "dw3_bwd"))
+                print(f"s{st}.{br:6s} fc2_dgrad*gp + dw3_bwd {pair:7.1f} us | fused {fus['FUSED dgrad+dw3']:7.1f} us")
+            if "FUSED fwd" in fus and not match:
                 print(f"s{st}.{br:6s} unfused fwd {sum(unf[:4]):7.1f} us bwd {sum(unf[4:]):7.1f} us | fused fwd "
                       f"{fus['FUSED fwd']:7.1f} us bwd {fus['FUSED bwd']:7.1f} us | fused fwd+g "
                       f"{fus['FUSED fwd+g']:7.1f} us")
-    allr = [r for r in allr if not r["kernel"].startswith("FUSED")]
-    tot = sum(r["us"] for r in allr)
-    ideal = sum(r["bytes"] for r in allr) / HBM * 1e6
+    unfused = [r for r in allr if not r["kernel"].startswith("FUSED")]  # the total line only: the JSON keeps every row
+    tot = sum(r["us"] for r in unfused)
+    ideal = sum(r["bytes"] for r in unfused) / HBM * 1e6
     print(f"total {tot:.1f} us, HBM ideal at 6.3 TB/s {ideal:.1f} us ({ideal / tot:.2f})")
     if out:
         with open(out, "w") as fh:
