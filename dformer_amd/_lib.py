@@ -156,6 +156,15 @@ _SIGS = {
     "dfm_conv3s1_col2im": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, c_int, P]),
     "dfm_conv3_weight_pack": (c_int, [c_int, c_int, c_int, c_int, P, P, P]),
     "dfm_conv3_weight_unpack": (c_int, [c_int, c_int, c_int, P, P, c_int, P]),
+    "dfm_conv3s1_igemm_supported": (c_int, [c_int, c_int, c_int]),
+    "dfm_conv3s1_igemm_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P, P, P, c_long, c_int,
+                                      P]),
+    "dfm_conv3_weight_pack_dgrad": (c_int, [c_int, c_int, c_int, P, P, P]),
+    "dfm_conv3s1_igemm_wgrad_workspace_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dfm_conv3s1_igemm_wgrad": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P, P, P,
+                                        c_size_t, P]),
+    "dfm_ppm_pool_fwd": (c_int, [c_int] * 9 + [P, c_long, P, c_long, P]),
+    "dfm_ppm_pool_bwd": (c_int, [c_int] * 9 + [P, c_long, P, c_long, c_int, P]),
     "dfm_resize_nchw": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long, P, c_int,
                                 c_int, c_int, c_int, P, P]),
     "dfm_msf_accumulate": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_long, c_int, c_int, c_int, c_int, c_int,

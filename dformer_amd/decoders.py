@@ -3,6 +3,7 @@
   LightHamHead (+ Hamburger, NMF2D)   models/decoders/ham_head.py:11-240, decode_head.py:55-231
   DecoderHead (MLPDecoder)            models/decoders/MLPDecoder.py:8-81
   FCNHead (auxiliary head)            models/decoders/fcnhead.py:9-29, builder.py:138-143
+  UPerHead (+ PPM)                    models/decoders/UPernet.py:8-146, builder.py:145-152
   seg_loss                            models/builder.py:203,230
 
 Feature maps are NHWC rows [B*h*w, C] in the compute dtype. BatchNorm runs in training mode on
@@ -14,7 +15,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import kernels as K
-from .functional import gslot, gslot2, gslot_rows, wcast
+from .functional import gslot, gslot2, gslot_rows, wcast, wpack3
 
 
 # Test-only: with an initialised one-rank process group, take every collective branch (SyncBN
@@ -842,6 +843,232 @@ class FCNHead(nn.Module):
         conv, bn = self.conv[0], self.conv[1]
         y = Conv3BNReLUFn.apply(rows, (B, H, W), conv.weight, conv.bias, bn.weight, bn.bias, bn, self.syncbn)
         logits = LinearActFn.apply(y, self.classifier.weight, self.classifier.bias, 0, False)
+        return logits.view(B, H, W, self.num_classes).permute(0, 3, 1, 2)
+
+
+# ================================================================================== UPerNet head
+def _bn_forward(y0, bn, sync):
+    """(mean, rstd, count) of a BatchNorm over rows y0: batch statistics in train mode (running statistics
+    updated), the running statistics as a fixed affine in eval mode."""
+    if bn.training:
+        return bn_batch_stats(y0, bn, sync)
+    return bn.running_mean, torch.rsqrt(bn.running_var + bn.eps), y0.shape[0]
+
+
+def _bn_relu_backward(dy, y0, y, mean, rstd, gamma, bn, sync, count, training):
+    """dy0 of y = relu(BN(y0)) and the BN's (dgamma, dbeta)."""
+    dy = K.relu_bwd(dy.contiguous(), y)
+    st2, dgamma, dbeta = bn_grad_stats(y0, dy, mean, rstd, bn, sync)
+    if training:
+        dy0 = K.bn_bwd_apply(y0, dy, mean, rstd, gamma, st2, count)
+    else:  # running statistics: BN is a fixed per-channel affine
+        dy0 = K.scale_mul(dy, colscale=rstd * gamma)
+    return dy0, dgamma, dbeta
+
+
+class Conv1BiasBNReLUFn(torch.autograd.Function):
+    """y = relu(BN(x @ W^T + b)) — UPerHead's 1x1 Sequential(Conv2d(bias), BN, ReLU) (UPernet.py:38-42,
+    128-133). The bias sits ahead of a BatchNorm: in train mode it only enters running_mean and its
+    gradient is zero up to rounding; in eval mode it matters."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, bn, sync):
+        y0 = K.linear(x, wcast(x.dtype, w), b.detach())
+        mean, rstd, count = _bn_forward(y0, bn, sync)
+        y = K.bn_apply(y0, mean, rstd, gamma, beta, act=2)
+        ctx.save_for_backward(x, w, b, y0, y, mean, rstd, gamma)
+        ctx.meta = (count, sync, bn, bn.training)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        K.TAG = "decoder.bwd"
+        x, w, b, y0, y, mean, rstd, gamma = ctx.saved_tensors
+        count, sync, bn, training = ctx.meta
+        dy0, dgamma, dbeta = _bn_relu_backward(dy, y0, y, mean, rstd, gamma, bn, sync, count, training)
+        dW, db = K.linear_wgrad(dy0, x, out=gslot2(w), bias_grad=True, bias_out=gslot(b))
+        dx = K.linear_dgrad(dy0, wcast(x.dtype, w)) if ctx.needs_input_grad[0] else None
+        return dx, dW.view_as(w), db, dgamma, dbeta, None, None
+
+
+class Conv3IgemmBNReLUFn(torch.autograd.Function):
+    """y = relu(BN(conv3x3(x) + b)) on NHWC rows with the implicit-GEMM conv (csrc/conv3_igemm.hip) —
+    UPerHead's bottleneck, fpn_convs and fpn_bottleneck (UPernet.py:29-33, 43-47, 51-55). The gathered
+    operand is formed inside the GEMM's tile loader in all three passes, so nothing of size P x 9*Cin is
+    allocated or saved: backward re-gathers x for the weight gradient and runs the same kernel on dy0 with
+    the transposed, flipped pack for the input gradient."""
+
+    @staticmethod
+    def forward(ctx, x, shape, w, b, gamma, beta, bn, sync):
+        y0 = K.conv3_igemm(x, shape, wpack3(x.dtype, w), b.detach())
+        mean, rstd, count = _bn_forward(y0, bn, sync)
+        y = K.bn_apply(y0, mean, rstd, gamma, beta, act=2)
+        ctx.save_for_backward(x, w, b, y0, y, mean, rstd, gamma)
+        ctx.meta = (shape, count, sync, bn, bn.training)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        K.TAG = "decoder.bwd"
+        x, w, b, y0, y, mean, rstd, gamma = ctx.saved_tensors
+        shape, count, sync, bn, training = ctx.meta
+        dy0, dgamma, dbeta = _bn_relu_backward(dy, y0, y, mean, rstd, gamma, bn, sync, count, training)
+        dwp, db = K.conv3_igemm_wgrad(dy0, x, shape, bias_grad=True, bias_out=gslot(b))
+        dw = K.conv3_weight_unpack(dwp, x.shape[1], dw=gslot(w))
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = K.conv3_igemm(dy0, shape, wpack3(x.dtype, w, dgrad=True))
+        return dx, None, dw, db, dgamma, dbeta, None, None
+
+
+class PpmPoolFn(torch.autograd.Function):
+    """The PPM's nn.AdaptiveAvgPool2d(s) for every scale in one launch (UPernet.py:129): rows [B*h*w, C] ->
+    one [B * sum s^2, C] buffer, scale-major, returned as its per-scale row blocks [B*s^2, C]."""
+
+    @staticmethod
+    def forward(ctx, x, shape, scales):
+        ctx.meta = (shape, scales)
+        B = shape[0]
+        pooled = K.ppm_pool(x, shape, scales)
+        offs = [0]
+        for s in scales:
+            offs.append(offs[-1] + B * s * s)
+        return tuple(pooled[offs[k]:offs[k + 1]] for k in range(len(scales)))
+
+    @staticmethod
+    def backward(ctx, *dys):
+        K.TAG = "decoder.bwd"
+        shape, scales = ctx.meta
+        B = shape[0]
+        ref = next(d for d in dys if d is not None)
+        dy = torch.empty(B * sum(s * s for s in scales), ref.shape[1], device=ref.device, dtype=ref.dtype)
+        off = 0
+        for s, d in zip(scales, dys):
+            blk = dy[off:off + B * s * s]
+            if d is None:
+                blk.zero_()
+            else:
+                K.scale_mul(d.contiguous(), out=blk)
+            off += B * s * s
+        return K.ppm_pool_bwd(dy, shape, scales), None, None
+
+
+class UpAddFn(torch.autograd.Function):
+    """fine + resize(coarse, size of fine, bilinear, align_corners=False) — one level of UPerHead's top-down
+    path (UPernet.py:78-84). The reference adds in place into the lateral's ReLU output, which autograd refuses
+    in training (ReLU's backward needs that output); the sum is formed out of place, the semantics upstream
+    mmsegmentation has."""
+
+    @staticmethod
+    def forward(ctx, fine, coarse, B, hw_fine, hw_coarse):
+        out = K.scale_mul(fine)
+        K.bilinear(coarse, hw_coarse, hw_fine, B, out=out, accumulate=True)
+        ctx.meta = (B, hw_fine, hw_coarse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        K.TAG = "decoder.bwd"
+        B, hw_fine, hw_coarse = ctx.meta
+        dout = dout.contiguous()
+        return dout, K.bilinear_bwd(dout, hw_coarse, hw_fine, B), None, None, None
+
+
+class PPM(nn.ModuleList):
+    """Pooling Pyramid Module parameter container (UPernet.py:107-146): one Sequential(AdaptiveAvgPool2d(s),
+    Conv2d 1x1, norm, ReLU) per scale, keys `{i}.1.*` / `{i}.2.*`. UPerHead runs it on kernels."""
+
+    def __init__(self, pool_scales, in_channel, channels, norm_layer, align_corners=False):
+        super().__init__()
+        self.pool_scales = tuple(pool_scales)
+        self.align_corners = align_corners
+        self.in_channel = in_channel
+        self.channels = channels
+        for s in self.pool_scales:
+            self.append(nn.Sequential(nn.AdaptiveAvgPool2d(s), nn.Conv2d(in_channel, channels, 1),
+                                      norm_layer(channels), nn.ReLU(inplace=True)))
+
+
+class UPerHead(nn.Module):
+    """UPerHead (UPernet.py:8-104) -> logits at 1/4 resolution, with the reference's submodule names and
+    registration order (state_dict keys, group_weight order). forward(list of 4 NCHW maps) -> logits NCHW view
+    of NHWC rows. Every conv carries a bias ahead of its BatchNorm like the reference; `dropout_ratio` is
+    accepted and unused (this head has no dropout). The four 3x3 convs run as implicit GEMMs."""
+
+    def __init__(self, in_channels=(96, 192, 384, 768), num_classes=40, channels=512, pool_scales=(1, 2, 3, 6),
+                 norm_layer=nn.BatchNorm2d, dropout_ratio=0.1, align_corners=False, bn_eps=1e-3, bn_momentum=0.1,
+                 syncbn=False):
+        super().__init__()
+        if align_corners:
+            raise NotImplementedError("UPerHead: only align_corners=False (builder.py:148) has kernels")
+        if len(pool_scales) > 4 or any(not 1 <= s <= 16 for s in pool_scales):
+            raise NotImplementedError("UPerHead: the pyramid pooling kernel takes up to 4 scales of 1..16")
+        self.in_channels = list(in_channels)
+        self.channels = channels
+        self.num_classes = num_classes
+        self.align_corners = align_corners
+        for cin in (self.in_channels[-1] + len(pool_scales) * channels, channels, len(self.in_channels) * channels):
+            if not K.conv3_igemm_supported(torch.float32, cin, channels) or self.in_channels[-1] % 8:
+                raise NotImplementedError(f"UPerHead: the implicit 3x3 conv and the pyramid pooling need channel "
+                                          f"counts that are multiples of 8, got in_channels {self.in_channels}, "
+                                          f"channels {channels}")
+        self.psp_modules = PPM(pool_scales, self.in_channels[-1], channels, norm_layer=norm_layer,
+                               align_corners=align_corners)
+        self.bottleneck = nn.Sequential(
+            nn.Conv2d(self.in_channels[-1] + len(pool_scales) * channels, channels, 3, padding=1),
+            norm_layer(channels), nn.ReLU(inplace=True))
+        self.lateral_convs = nn.ModuleList()
+        self.fpn_convs = nn.ModuleList()
+        for cin in self.in_channels[:-1]:  # skip the top layer
+            self.lateral_convs.append(nn.Sequential(nn.Conv2d(cin, channels, 1), norm_layer(channels),
+                                                    nn.ReLU(inplace=False)))
+            self.fpn_convs.append(nn.Sequential(nn.Conv2d(channels, channels, 3, padding=1), norm_layer(channels),
+                                                nn.ReLU(inplace=False)))
+        self.fpn_bottleneck = nn.Sequential(nn.Conv2d(len(self.in_channels) * channels, channels, 3, padding=1),
+                                            norm_layer(channels), nn.ReLU(inplace=True))
+        self.conv_seg = nn.Conv2d(channels, num_classes, kernel_size=1)
+        for m in self.modules():
+            if isinstance(m, nn.modules.batchnorm._BatchNorm):
+                m.eps, m.momentum = bn_eps, bn_momentum
+        self.syncbn = syncbn or isinstance(self.bottleneck[1], nn.SyncBatchNorm)
+
+    def _conv1(self, seq, x):
+        conv, bn = seq[-3], seq[-2]
+        return Conv1BiasBNReLUFn.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn, self.syncbn)
+
+    def _conv3(self, seq, x, shape):
+        conv, bn = seq[0], seq[1]
+        return Conv3IgemmBNReLUFn.apply(x, shape, conv.weight, conv.bias, bn.weight, bn.bias, bn, self.syncbn)
+
+    def psp_forward(self, x, shape):
+        """UPernet.py:58-66 on rows: pool, per-scale 1x1 conv + BN (over B*s^2 rows) + ReLU, upsample, concat
+        after the input, 3x3 bottleneck."""
+        B, h, w = shape
+        scales = self.psp_modules.pool_scales
+        pooled = PpmPoolFn.apply(x, shape, scales)
+        outs, hw = [x], [(h, w)]
+        for s, seq, rows in zip(scales, self.psp_modules, pooled):
+            outs.append(self._conv1(seq, rows))
+            hw.append((s, s))
+        return self._conv3(self.bottleneck, ResizeCatFn.apply(B, hw, *outs), shape)
+
+    def forward(self, inputs):
+        rows, hw = [], []
+        B = inputs[0].shape[0]
+        for f in inputs:
+            r, (b, h, w) = _nhwc_rows(f)
+            rows.append(r)
+            hw.append((h, w))
+        n = len(rows)
+        laterals = [self._conv1(seq, rows[i]) for i, seq in enumerate(self.lateral_convs)]
+        laterals.append(self.psp_forward(rows[-1], (B,) + hw[-1]))
+        for i in range(n - 1, 0, -1):  # top-down path
+            laterals[i - 1] = UpAddFn.apply(laterals[i - 1], laterals[i], B, hw[i - 1], hw[i])
+        outs = [self._conv3(self.fpn_convs[i], laterals[i], (B,) + hw[i]) for i in range(n - 1)]
+        outs.append(laterals[-1])
+        H, W = hw[0]
+        x = self._conv3(self.fpn_bottleneck, ResizeCatFn.apply(B, hw, *outs), (B, H, W))
+        logits = LinearActFn.apply(x, self.conv_seg.weight, self.conv_seg.bias, 0, False)
         return logits.view(B, H, W, self.num_classes).permute(0, 3, 1, 2)
 
 

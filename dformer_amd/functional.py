@@ -81,6 +81,21 @@ def wcast(dtype, *params):
     return w
 
 
+def wpack3(dtype, w, dgrad=False):
+    """Packed compute-dtype copy of a 3x3 conv weight for the implicit-GEMM conv (K.conv3_igemm), cached per
+    epoch like wcast's casts: [cout, 9*cin] (dfm_conv3_weight_pack's layout), or with dgrad the [cin, 9*cout]
+    pack of the transposed, spatially flipped weight that turns the same kernel into the input gradient."""
+    key = (id(w), dtype, "pack3T" if dgrad else "pack3")
+    ptrs = (w.data_ptr(), w._version)  # an in-place update by a torch optimizer bumps the version
+    hit = _WCACHE.get(key)
+    if hit is not None and hit[0] == _EPOCH[0] and hit[2] == ptrs and hit[3][0]() is w:
+        return hit[1]
+    wd = w.detach()
+    wp = K.conv3_weight_pack_dgrad(wd, dtype) if dgrad else K.conv3_weight_pack(wd, dtype, 9 * wd.shape[1])
+    _WCACHE[key] = (_EPOCH[0], wp, ptrs, (weakref.ref(w),))
+    return wp
+
+
 _GSLOT = {}
 
 

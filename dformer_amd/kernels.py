@@ -925,6 +925,99 @@ def conv3_weight_unpack(dwp, cin, dw=None, accumulate=False):
     return dw
 
 
+# ------------------------------------ implicit-GEMM 3x3 conv + pyramid pooling (UPerNet head)
+def conv3_igemm_supported(dtype, cin, cout):
+    code = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}.get(dtype, -1)
+    return bool(lib.dfm_conv3s1_igemm_supported(code, cin, cout))
+
+
+def conv3_igemm(x, shape, wp, bias=None, out=None, accumulate=False):
+    """y [B*H*W, cout] (+)= conv3x3(x, stride 1, pad 1) + bias on NHWC rows x [B*H*W, cin] (a column slice of a
+    wider buffer is fine, as is `out`), wp [cout, 9*cin] the packed weight. No gathered operand is formed.
+    With the pack of conv3_weight_pack_dgrad and x = dy this is the conv's input gradient."""
+    B, H, W = shape
+    cin = x.shape[1]
+    cout = wp.shape[0]
+    assert wp.shape[1] == 9 * cin and wp.is_contiguous() and wp.dtype == x.dtype, (tuple(wp.shape), cin)
+    if out is None:
+        out = torch.empty(B * H * W, cout, device=x.device, dtype=x.dtype)
+        accumulate = False
+    check(lib.dfm_conv3s1_igemm_fwd(dtype_code(x), B, H, W, cin, cout, ptr(x), ld(x), ptr(wp), ptr(bias), ptr(out),
+                                    ld(out), int(accumulate), stream()), "dfm_conv3s1_igemm_fwd")
+    if ACCOUNT is not None:
+        P = B * H * W
+        _acct(2.0 * P * cout * 9 * cin, _es(x) * (P * cin + P * cout * (1 + bool(accumulate)) + 9 * cin * cout),
+              "bf16" if x.dtype != torch.float32 else "f32")
+    return out
+
+
+def conv3_weight_pack_dgrad(w, dtype):
+    """[cin, 9*cout] pack of w.permute(1, 0, 2, 3).flip(2, 3): conv3_igemm on dy with it is the input gradient."""
+    cout, cin = w.shape[:2]
+    out = torch.empty(cin, 9 * cout, device=w.device, dtype=dtype)
+    check(lib.dfm_conv3_weight_pack_dgrad(dtype_code(out), cout, cin, ptr(w), ptr(out), stream()),
+          "dfm_conv3_weight_pack_dgrad")
+    if ACCOUNT is not None:
+        _acct(0, w.numel() * 4 + out.numel() * _es(out))
+    return out
+
+
+def conv3_igemm_wgrad(dy, x, shape, bias_grad=False, bias_out=None):
+    """dwp [cout, 9*cin] float32 (packed layout, for conv3_weight_unpack) = sum_p dy[p]^T (x) gathered x[p];
+    bias_grad=True also db [cout] = sum_p dy[p] (into `bias_out` when given). Split-K over pixels with a
+    fixed-order second stage: bit-reproducible."""
+    B, H, W = shape
+    cin, cout = x.shape[1], dy.shape[1]
+    dwp = torch.empty(cout, 9 * cin, device=dy.device, dtype=torch.float32)
+    db = None
+    if bias_grad:
+        db = bias_out if bias_out is not None else torch.empty(cout, device=dy.device, dtype=torch.float32)
+    need = lib.dfm_conv3s1_igemm_wgrad_workspace_size(dtype_code(dy), B, H, W, cin, cout, int(bias_grad))
+    ws = _ws(need, dy.device)
+    check(lib.dfm_conv3s1_igemm_wgrad(dtype_code(dy), B, H, W, cin, cout, ptr(dy), ld(dy), ptr(x), ld(x), ptr(dwp),
+                                      ptr(db), ptr(ws), ws.numel() if ws is not None else 0, stream()),
+          "dfm_conv3s1_igemm_wgrad")
+    if ACCOUNT is not None:
+        P = B * H * W
+        _acct(2.0 * P * cout * 9 * cin, _es(x) * P * (cin + cout) + 4 * (9 * cin + 1) * cout,
+              "bf16" if x.dtype != torch.float32 else "f32")
+    return (dwp, db) if bias_grad else dwp
+
+
+def _scales4(scales):
+    s = tuple(int(v) for v in scales)
+    assert 1 <= len(s) <= 4, "pyramid pooling takes 1..4 scales"
+    return s + (0,) * (4 - len(s))
+
+
+def ppm_pool(x, shape, scales, out=None):
+    """nn.AdaptiveAvgPool2d(s) of NHWC rows x [B*H*W, C] for every s in `scales` in one launch:
+    [B * sum s^2, C], scale-major (scale k owns rows [B*off_k, B*off_{k+1}), the NHWC rows of a B x s x s map)."""
+    B, H, W = shape
+    C = x.shape[1]
+    rows = B * sum(s * s for s in scales)
+    if out is None:
+        out = torch.empty(rows, C, device=x.device, dtype=x.dtype)
+    check(lib.dfm_ppm_pool_fwd(dtype_code(x), B, H, W, C, *_scales4(scales), ptr(x), ld(x), ptr(out), ld(out),
+                               stream()), "dfm_ppm_pool_fwd")
+    if ACCOUNT is not None:
+        _acct(0, (B * H * W * len(scales) + rows) * C * _es(x))
+    return out
+
+
+def ppm_pool_bwd(dy, shape, scales, dx=None, accumulate=False):
+    B, H, W = shape
+    C = dy.shape[1]
+    if dx is None:
+        dx = torch.empty(B * H * W, C, device=dy.device, dtype=dy.dtype)
+        accumulate = False
+    check(lib.dfm_ppm_pool_bwd(dtype_code(dy), B, H, W, C, *_scales4(scales), ptr(dy), ld(dy), ptr(dx), ld(dx),
+                               int(accumulate), stream()), "dfm_ppm_pool_bwd")
+    if ACCOUNT is not None:
+        _acct(0, (B * H * W * (1 + bool(accumulate)) + dy.shape[0]) * C * _es(dy))
+    return dx
+
+
 # ------------------------------------------------------------------ multi-scale + flip eval
 def resize_nchw(x, size, align_corners, flip=False, dtype=torch.float32):
     """F.interpolate(x, size, 'bilinear', align_corners) [then torch.flip(dims=(3,))], x any strides."""

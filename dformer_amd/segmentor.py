@@ -7,12 +7,15 @@ tuple through and crashes, SURVEY.md §3.0 #2 — the intended upstream semantic
 materialised when `return_logits` is True (the loss itself is fused and never needs it).
 With `decoder == "ham"` and a non-zero `cfg.aux_rate` an auxiliary FCNHead reads the stage-2 map and the
 training loss is CE(main) + aux_rate * CE(aux) (builder.py:138-143, 204-207, 231-232); no eval path runs it.
+`decoder == "UPernet"` builds UPerHead on all four maps (logits at 1/4 resolution) and always the aux head
+with aux_rate 0.4 (builder.py:145-152).
 """
 import torch
 import torch.nn as nn
 
 from . import kernels as K
-from .decoders import DecoderHead, FCNHead, FssLossFn, FssProtoSimFn, LightHamHead, SegLossFn, _nhwc_rows
+from .decoders import (DecoderHead, FCNHead, FssLossFn, FssProtoSimFn, LightHamHead, SegLossFn, UPerHead,
+                       _nhwc_rows)
 from .encoder import DFormer_Base, DFormer_Large, DFormer_Small, DFormer_Tiny, get_DFormerTrav
 from .functional import invalidate_weights
 
@@ -66,11 +69,20 @@ class EncoderDecoder(nn.Module):
             self.decode_head = LightHamHead(in_channels=self.channels[1:], num_classes=cfg.num_classes,
                                             in_index=[1, 2, 3], norm_cfg=norm_cfg, channels=cfg.decoder_embed_dim,
                                             bn_eps=bn_eps, bn_momentum=bn_mom)
+        elif cfg.decoder == "UPernet":
+            self.decode_head = UPerHead(in_channels=self.channels, num_classes=cfg.num_classes, norm_layer=norm_layer,
+                                        channels=512, bn_eps=bn_eps, bn_momentum=bn_mom, syncbn=syncbn)
         else:
             raise NotImplementedError(f"decoder {cfg.decoder!r} is outside the hot path (SURVEY.md §2)")
         self.aux_head = None
         self.aux_rate = 0
-        if cfg.decoder == "ham" and _aux_rate(cfg) != 0:
+        if cfg.decoder == "UPernet":
+            # builder.py:149-152: the aux head and its rate are hard-coded, whatever cfg.aux_rate says
+            self.aux_index = 2
+            self.aux_rate = 0.4
+            self.aux_head = FCNHead(self.channels[2], cfg.num_classes, norm_layer=norm_layer, bn_eps=bn_eps,
+                                    bn_momentum=bn_mom, syncbn=syncbn)
+        elif cfg.decoder == "ham" and _aux_rate(cfg) != 0:
             # builder.py:138-143: FCNHead(self.channels[2], cfg.num_classes, ...) binds cfg.num_classes to
             # the hidden width `channels`; the head's own num_classes stays 40 whatever the config says
             self.aux_index = 2

@@ -440,6 +440,47 @@ int dfm_conv3_weight_pack(int dtype_out, int Cout, int Cin, int Kp, const float*
 int dfm_conv3_weight_unpack(int Cout, int Cin, int Kp, const float* dwp, float* dw, int accumulate,
                             dfm_stream_t stream);
 
+/* ---------------------------------------------------------------- UPerNet head (models/decoders/UPernet.py)
+ * Implicit-GEMM 3x3 stride-1 pad-1 conv on NHWC rows (conv3_igemm.hip): the operand of
+ * dfm_conv3s1_im2col is gathered inside the MFMA GEMM's tile loader, so nothing of size P x 9*Cin exists.
+ * New symbols only: dfm_abi_version() stays 13. fp32 / bf16 / f16 operands, fp32 accumulation; Cin % 8 == 0;
+ * x / y / dy 16-byte aligned with row strides that are multiples of 8 (ldx >= Cin, ldy >= Cout), so a conv
+ * reads a channel slice of a wider buffer and writes into one. Enqueue-only, no host synchronisation.
+ * fwd (UPernet.py:30,44,52 forward; the same kernel is the input gradient):
+ *   y[p][o] (+)= bias[o] + sum_{tap,c} x[nbr(p,tap)][c] * wp[o][tap*Cin + c],  p = (b*H + y)*W + x, pixels
+ *   outside the image contribute zero; wp [Cout][9*Cin] is dfm_conv3_weight_pack's (Kp == 9*Cin), bias may be
+ *   NULL. The input gradient of the conv is fwd on dy (Cin and Cout swapped) with the pack of
+ *   dfm_conv3_weight_pack_dgrad; accumulate != 0 adds into y (dx).
+ * weight_pack_dgrad: wpt[c][tap*Cout + o] = w[o][c][8 - tap] (the transposed, spatially flipped weight
+ *   w.permute(1,0,2,3).flip(2,3) in dfm_conv3_weight_pack's column order), w float32 [Cout][Cin][3][3].
+ * wgrad (UPernet.py:30,44,52 backward): dwp[o][tap*Cin + c] = sum_p dy[p][o] * x[nbr(p,tap)][c] as fp32 in
+ *   packed layout (dfm_conv3_weight_unpack then writes the parameter slot); db[o] = sum_p dy[p][o] rides
+ *   along as the virtual all-ones column (db may be NULL). Split-K over pixels into the caller's workspace
+ *   (dfm_conv3s1_igemm_wgrad_workspace_size bytes, 0 when unsplit) with a fixed-order second stage: no float
+ *   atomics, a second run is bit-identical. Needs Cout % 8 == 0 too.
+ * supported: 1 when (dtype, Cin, Cout) can run, else 0. Unsupported or misshapen arguments return a negative
+ *   status with dfm_last_error() set before any launch. */
+int dfm_conv3s1_igemm_supported(int dtype, int Cin, int Cout);
+int dfm_conv3s1_igemm_fwd(int dtype, int B, int H, int W, int Cin, int Cout, const void* x, long ldx,
+                          const void* wp, const float* bias, void* y, long ldy, int accumulate,
+                          dfm_stream_t stream);
+int dfm_conv3_weight_pack_dgrad(int dtype_out, int Cout, int Cin, const float* w, void* wpt, dfm_stream_t stream);
+size_t dfm_conv3s1_igemm_wgrad_workspace_size(int dtype, int B, int H, int W, int Cin, int Cout, int bias_grad);
+int dfm_conv3s1_igemm_wgrad(int dtype, int B, int H, int W, int Cin, int Cout, const void* dy, long lddy,
+                            const void* x, long ldx, float* dwp, float* db, void* workspace,
+                            size_t workspace_bytes, dfm_stream_t stream);
+/* Pyramid pooling (UPernet.py:126-133: nn.AdaptiveAvgPool2d(s) for up to 4 scales, s <= 16, 0 = unused) in
+ * one launch: NHWC rows x [B*H*W][ldx] -> y [B * sum s^2][ldy], scale-major (scale k owns rows
+ * [B*off_k, B*off_{k+1}), off_k = sum_{j<k} s_j^2, ordered (b, i, j) inside, i.e. the NHWC rows of a
+ * B x s x s map). Bins are torch's: rows [floor(i*H/s), ceil((i+1)*H/s)), so they overlap when H % s != 0
+ * and repeat a pixel when H < s. fp32 accumulation in a fixed order. C % 8 == 0, 16-byte aligned operands.
+ * bwd: dx[p][c] (+)= sum over the bins that hold p of dy[bin][c] / |bin|, one owner per element, scales and
+ * bins in ascending order (bit-reproducible). */
+int dfm_ppm_pool_fwd(int dtype, int B, int H, int W, int C, int s0, int s1, int s2, int s3, const void* x, long ldx,
+                     void* y, long ldy, dfm_stream_t stream);
+int dfm_ppm_pool_bwd(int dtype, int B, int H, int W, int C, int s0, int s1, int s2, int s3, const void* dy,
+                     long lddy, void* dx, long lddx, int accumulate, dfm_stream_t stream);
+
 /* ---------------------------------------------------------------- multi-scale + flip evaluation
  * utils/val_mm.py:325-472 evaluate_msf, utils/metrics_new.py:16-20 Metrics.update.
  * resize_nchw: y [B][C][Ho][Wo] (contiguous) = F.interpolate(x, (Ho, Wo), 'bilinear',
