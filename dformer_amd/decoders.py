@@ -6,138 +6,49 @@
   UPerHead (+ PPM)                    models/decoders/UPernet.py:8-146, builder.py:145-152
   seg_loss                            models/builder.py:203,230
 
-Feature maps are NHWC rows [B*h*w, C] in the compute dtype. BatchNorm runs in training mode on
-batch statistics; with a multi-rank process group and SyncBN, the (sum, sumsq) and the backward
-(sum dy, sum dy*xhat) statistics are all-reduced (SyncBatchNorm semantics).
+Feature maps are NHWC rows [B*h*w, C] in the compute dtype. Every BatchNorm goes through
+batchnorm.bn_forward / bn_backward (batch statistics and SyncBN in train mode, the running statistics
+as a fixed affine in eval mode).
 """
 import torch
-import torch.distributed as dist
 import torch.nn as nn
 
 from . import kernels as K
-from .functional import gslot, gslot2, gslot_rows, wcast, wpack3
-
-
-# Test-only: with an initialised one-rank process group, take every collective branch (SyncBN
-# all-gather / all-reduce, bucketed gradient all-reduce, loss all-reduce) as if world > 1, so the
-# multi-rank code runs (and is captured into HIP graphs) on a single GPU (tests/test_graph_gpu.py).
-FORCE_COLLECTIVES = False
-
-
-def collectives_on(world=None):
-    """True when the data-parallel collective branches run: world > 1, or FORCE_COLLECTIVES with an
-    initialised process group."""
-    if not (dist.is_available() and dist.is_initialized()):
-        return False
-    w = dist.get_world_size() if world is None else world
-    return w > 1 or FORCE_COLLECTIVES
-
-
-def _world(sync):
-    if sync and dist.is_available() and dist.is_initialized():
-        return dist.get_world_size()
-    return 1
-
-
-# Per-rank row counts of a SyncBN batch, keyed by (local rows, world): data-parallel ranks see the
-# same batch shape every step, so the counts are exchanged (and read on the host) once per shape.
-_GLOBAL_ROWS = {}
-_GLOBAL_TOTAL = {}
-
-
-def bn_batch_stats(x, bn, sync):
-    """Train-mode BatchNorm / SyncBatchNorm statistics of NHWC rows x: (mean, rstd, count), with the
-    running statistics updated like torch (momentum, unbiased variance). With SyncBN over a
-    multi-rank group the per-rank shifted sums are all-gathered into one [world, 3, C] buffer and
-    merged on the device (K.bn_merge; torch SyncBatchNorm all-gathers (mean, invstd, count) the
-    same way, torch/nn/modules/_functions.py)."""
-    st = K.bn_stats(x)
-    rows = x.shape[0]
-    world = _world(sync)
-    count = rows
-    if sync and collectives_on(world):
-        # gathered along dim 0 as [world * 3, C] (gloo splits the output along its first dim and
-        # requires each piece to have the input's shape; RCCL takes either form)
-        gathered = torch.empty((world * st.shape[0],) + tuple(st.shape[1:]), device=st.device, dtype=st.dtype)
-        dist.all_gather_into_tensor(gathered, st)
-        gathered = gathered.view((world,) + tuple(st.shape))
-        counts = _GLOBAL_ROWS.get((rows, world))
-        if counts is None:  # first batch of this shape: exchange the per-rank row counts once
-            cnt = torch.tensor([float(rows)], device=x.device)
-            counts = torch.empty(world, device=x.device)
-            dist.all_gather_into_tensor(counts, cnt)
-            _GLOBAL_ROWS[(rows, world)] = counts
-        st = K.bn_merge(gathered, counts)
-        total = _GLOBAL_TOTAL.get((rows, world))
-        if total is None:  # one host read per batch shape, not one per BN layer per step
-            total = _GLOBAL_TOTAL[(rows, world)] = int(counts.sum().item())
-        count = total
-    mean, rstd = K.bn_finalize(st, count, bn.eps, bn.momentum if bn.momentum is not None else 0.1, bn.running_mean,
-                               bn.running_var)
-    bn.num_batches_tracked.add_(1)
-    return mean, rstd, count
-
-
-# test-only probe (tests/test_dp_gpu.py): when a dict, bn_grad_stats records per BN layer (by id) the
-# float64 sums [sum dy*xhat, sum dy, sum |dy*xhat|, sum |dy|] of the rows it reduces, from the same
-# dy / x / mean / rstd its kernel reads
-BN_PROBE = None
-
-
-def bn_grad_stats(x, dy, mean, rstd, bn, sync):
-    """BatchNorm backward statistics st2 = (sum dy, sum dy * xhat) of NHWC rows. Returns (st2 for the
-    input gradient, dgamma, dbeta). The local statistics ARE this rank's beta / gamma gradients
-    (SyncBatchNorm's backward forms grad_weight / grad_bias before its all-reduce,
-    torch/nn/modules/_functions.py; DDP then averages them like every gradient) and are written
-    straight into the flat gradient slots, laid out [beta | gamma] by train.fused_chains; under
-    SyncBN an all-reduced copy feeds the input gradient."""
-    out = gslot_rows(bn.bias, bn.weight) if bn is not None and bn.affine else None
-    if BN_PROBE is not None and bn is not None:
-        dyd = dy.double()
-        t = dyd * ((x.double() - mean.double()) * rstd.double())
-        BN_PROBE[id(bn)] = torch.stack([t.sum(0), dyd.sum(0), t.abs().sum(0), dyd.abs().sum(0)])
-    st = K.bn_bwd_stats(x, dy, mean, rstd, out=out.view(2, -1) if out is not None else None)
-    stg = st
-    if sync and collectives_on():
-        stg = st.clone()
-        dist.all_reduce(stg)
-    return stg, st[1], st[0]
+from .batchnorm import bn_backward, bn_forward
+from .functional import gslot, gslot2, wcast, wpack3
 
 
 # ============================================================================ building blocks
-class ConvBNActFn(torch.autograd.Function):
-    """y = act(BN(x @ W^T) [+ res])  — mmcv ConvModule(1x1 conv, BN, ReLU) (ham_head.py:204-220)."""
+class Conv1BNActFn(torch.autograd.Function):
+    """y = act(BN(x @ W^T [+ b]) [+ res]) — mmcv ConvModule(1x1 conv, BN, ReLU) (ham_head.py:204-220) and, with
+    a conv bias, UPerHead's 1x1 Sequential(Conv2d(bias), BN, ReLU) (UPernet.py:38-42, 128-133). A bias ahead
+    of a BatchNorm only enters running_mean in train mode and its gradient is zero up to rounding; in eval
+    mode it matters."""
 
     @staticmethod
-    def forward(ctx, x, res, w, gamma, beta, bn, act, sync):
-        dt = x.dtype
-        Wc = wcast(dt, w)
-        y0 = K.linear(x, Wc)
-        rows = x.shape[0]
-        if bn.training:
-            mean, rstd, count = bn_batch_stats(y0, bn, sync)
-        else:
-            mean = bn.running_mean
-            rstd = torch.rsqrt(bn.running_var + bn.eps)
-            count = rows
+    def forward(ctx, x, res, w, b, gamma, beta, bn, act, sync):
+        y0 = K.linear(x, wcast(x.dtype, w), b.detach() if b is not None else None)
+        mean, rstd, count = bn_forward(y0, bn, sync)
         y = K.bn_apply(y0, mean, rstd, gamma, beta, res=res, act=act)
-        ctx.save_for_backward(x, w, y0, y, mean, rstd, gamma)
-        ctx.act, ctx.sync, ctx.count, ctx.has_res, ctx.bn = act, sync, count, res is not None, bn
+        ctx.save_for_backward(x, w, b, y0, y, mean, rstd, gamma)
+        ctx.meta = (act, sync, count, res is not None, bn, bn.training)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         K.TAG = "decoder.bwd"
-        x, w, y0, y, mean, rstd, gamma = ctx.saved_tensors
+        x, w, b, y0, y, mean, rstd, gamma = ctx.saved_tensors
+        act, sync, count, has_res, bn, training = ctx.meta
         dy = dy.contiguous()
-        if ctx.act == 2:
+        if act == 2:  # here, not in bn_backward: the residual's gradient is the dy behind the ReLU
             dy = K.relu_bwd(dy, y)
-        st2, dgamma, dbeta = bn_grad_stats(y0, dy, mean, rstd, ctx.bn, ctx.sync)
-        dy0 = K.bn_bwd_apply(y0, dy, mean, rstd, gamma, st2, ctx.count)
-        dW = K.linear_wgrad(dy0, x, out=gslot2(w))
-        dx = K.linear_dgrad(dy0, wcast(x.dtype, w))
-        dres = dy if ctx.has_res else None
-        return dx, dres, dW.view_as(w), dgamma, dbeta, None, None, None
+        dy0, dgamma, dbeta = bn_backward(dy, y0, (mean, rstd, count), gamma, bn, sync, training)
+        if b is None:
+            dW, db = K.linear_wgrad(dy0, x, out=gslot2(w)), None
+        else:
+            dW, db = K.linear_wgrad(dy0, x, out=gslot2(w), bias_grad=True, bias_out=gslot(b))
+        dx = K.linear_dgrad(dy0, wcast(x.dtype, w)) if ctx.needs_input_grad[0] else None
+        return dx, dy if has_res else None, dW.view_as(w), db, dgamma, dbeta, None, None, None
 
 
 class LinearActFn(torch.autograd.Function):
@@ -250,14 +161,10 @@ class SqueezeFoldFn(torch.autograd.Function):
                     y0 = K.bilinear(t, (h, wd), (H0, W0), B)
                 else:
                     K.bilinear(t, (h, wd), (H0, W0), B, out=y0, accumulate=True)
-        count = y0.shape[0]
-        if bn.training:
-            mean, rstd, count = bn_batch_stats(y0, bn, sync)
-        else:
-            mean, rstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
+        mean, rstd, count = bn_forward(y0, bn, sync)
         y = K.bn_apply(y0, mean, rstd, gamma, beta, act=2)
         ctx.save_for_backward(y0, y, mean, rstd, gamma, w, *rows)
-        ctx.meta = (B, hw, count, sync, bn, offs)
+        ctx.meta = (B, hw, count, sync, bn, bn.training, offs)
         return y
 
     @staticmethod
@@ -265,12 +172,10 @@ class SqueezeFoldFn(torch.autograd.Function):
         K.TAG = "decoder.bwd"
         y0, y, mean, rstd, gamma, w = ctx.saved_tensors[:6]
         rows = ctx.saved_tensors[6:]
-        B, hw, count, sync, bn, offs = ctx.meta
+        B, hw, count, sync, bn, training, offs = ctx.meta
         H0, W0 = hw[0]
         E = w.shape[0]
-        dy = K.relu_bwd(dy.contiguous(), y)
-        st2, dgamma, dbeta = bn_grad_stats(y0, dy, mean, rstd, bn, sync)
-        dy0 = K.bn_bwd_apply(y0, dy, mean, rstd, gamma, st2, count)
+        dy0, dgamma, dbeta = bn_backward(dy, y0, (mean, rstd, count), gamma, bn, sync, training, relu_y=y)
         dW = gslot2(w)
         if dW is None:
             dW = torch.empty(E, offs[-1], device=y0.device, dtype=torch.float32)
@@ -502,7 +407,8 @@ class ConvModule(nn.Module):
             self.bn = nn.BatchNorm2d(cout, eps=bn_eps)
 
     def fused(self, x, act, res=None, sync=False):
-        return ConvBNActFn.apply(x, res, self.conv.weight, self.bn.weight, self.bn.bias, self.bn, act, sync)
+        return Conv1BNActFn.apply(x, res, self.conv.weight, self.conv.bias, self.bn.weight, self.bn.bias, self.bn,
+                                  act, sync)
 
 
 class NMF2D(nn.Module):
@@ -563,6 +469,27 @@ def _nhwc_rows(t):
     return t.permute(0, 2, 3, 1).contiguous().view(B * H * W, C), (B, H, W)
 
 
+def _rows_hw(maps):
+    """NCHW maps -> (their NHWC rows, their (h, w))."""
+    rows, shapes = zip(*map(_nhwc_rows, maps))
+    return rows, [s[1:] for s in shapes]
+
+
+def _logits_nchw(logits, B, hw):
+    """Logit rows [B*H*W, ncls] -> their NCHW view [B, ncls, H, W]."""
+    return logits.view(B, *hw, logits.shape[1]).permute(0, 3, 1, 2)
+
+
+def _dropout2d_scale(head, B, width, dev):
+    """Dropout2d of a head as a [B, width] per-image channel scale mask / keep (decode_head.py:226-231), from
+    the head's injected keep masks if any; None when inactive."""
+    if not (head.training and head.dropout_ratio > 0):
+        return None
+    keep = 1.0 - head.dropout_ratio
+    mask = head.dropout_masks if head.dropout_masks is not None else (torch.rand(B, width, device=dev) < keep)
+    return mask.to(device=dev, dtype=torch.float32) / keep
+
+
 class LightHamHead(nn.Module):
     """LightHamHead (ham_head.py:184-240) + BaseDecodeHead pieces (decode_head.py:55-231).
     forward(list of 4 NCHW maps) -> logits NCHW view of NHWC rows [B, ncls, H/8, W/8]."""
@@ -594,25 +521,16 @@ class LightHamHead(nn.Module):
 
     def forward(self, inputs):
         feats = [inputs[i] for i in self.in_index]
-        rows, hw = [], []
         B = feats[0].shape[0]
-        for f in feats:
-            r, (b, h, w) = _nhwc_rows(f)
-            rows.append(r)
-            hw.append((h, w))
+        rows, hw = _rows_hw(feats)
         sq = self.squeeze
         x = SqueezeFoldFn.apply(B, hw, sq.bn, self.syncbn, sq.conv.weight, sq.bn.weight, sq.bn.bias, *rows)
         H, W = hw[0]
         x = self.hamburger.fused(x, B, H * W, self.syncbn)
         x = self.align.fused(x, act=2, sync=self.syncbn)
-        scale = None
-        if self.training and self.dropout_ratio > 0:
-            keep = 1.0 - self.dropout_ratio
-            mask = self.dropout_masks if self.dropout_masks is not None else \
-                (torch.rand(B, self.channels, device=x.device) < keep)
-            scale = mask.to(device=x.device, dtype=torch.float32) / keep
+        scale = _dropout2d_scale(self, B, self.channels, x.device)
         logits = ChannelDropoutLinearFn.apply(x, scale, B, self.conv_seg.weight, self.conv_seg.bias)
-        return logits.view(B, H, W, self.num_classes).permute(0, 3, 1, 2)
+        return _logits_nchw(logits, B, hw[0])
 
 
 class _Proj(nn.Module):
@@ -647,24 +565,17 @@ class DecoderHead(nn.Module):
 
     def forward(self, inputs):
         B = inputs[0].shape[0]
-        lvl, hw = [], []
+        rows, hw = _rows_hw(inputs[:4])
+        lvl = []
         for i in range(4):  # c1 (finest, the output resolution) .. c4
-            r, (b, h, w) = _nhwc_rows(inputs[i])
             lin = getattr(self, f"linear_c{i + 1}").proj
-            lvl += [r, lin.weight, lin.bias]
-            hw.append((h, w))
-        H, W = hw[0]
+            lvl += [rows[i], lin.weight, lin.bias]
         E = self.embed_dim
         fuse, bn = self.linear_fuse[0], self.linear_fuse[1]
         x = MLPFoldFn.apply(B, hw, E, bn, self.syncbn, fuse.weight, fuse.bias, bn.weight, bn.bias, *lvl)
-        scale = None
-        if self.training and self.dropout_ratio > 0:
-            keep = 1.0 - self.dropout_ratio
-            mask = self.dropout_masks if self.dropout_masks is not None else \
-                (torch.rand(B, E, device=x.device) < keep)
-            scale = mask.to(device=x.device, dtype=torch.float32) / keep
+        scale = _dropout2d_scale(self, B, E, x.device)
         logits = ChannelDropoutLinearFn.apply(x, scale, B, self.linear_pred.weight, self.linear_pred.bias)
-        return logits.view(B, H, W, self.num_classes).permute(0, 3, 1, 2)
+        return _logits_nchw(logits, B, hw[0])
 
 
 def _mm32(a, b, out, a_t=False, b_t=False, beta=0.0):
@@ -714,14 +625,10 @@ class MLPFoldFn(torch.autograd.Function):
                 K.linear(rows[i], Wpc[i], out=y0, beta=1.0)
             else:  # at the level's own resolution, then upsampled into the sum
                 K.bilinear(K.linear(rows[i], Wpc[i]), (h, w), (H0, W0), B, out=y0, accumulate=True)
-        count = y0.shape[0]
-        if bn.training:
-            mean, rstd, count = bn_batch_stats(y0, bn, sync)
-        else:
-            mean, rstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
+        mean, rstd, count = bn_forward(y0, bn, sync)
         y = K.bn_apply(y0, mean, rstd, gamma, beta, act=2)
         ctx.save_for_backward(y0, y, mean, rstd, gamma, wf, bf, *rows, *Ls, *bs, *Wpc)
-        ctx.meta = (B, hw, E, count, sync, bn)
+        ctx.meta = (B, hw, E, count, sync, bn, bn.training)
         return y
 
     @staticmethod
@@ -730,12 +637,10 @@ class MLPFoldFn(torch.autograd.Function):
         sv = ctx.saved_tensors
         y0, y, mean, rstd, gamma, wf, bf = sv[:7]
         rows, Ls, bs, Wpc = sv[7:11], sv[11:15], sv[15:19], sv[19:23]
-        B, hw, E, count, sync, bn = ctx.meta
+        B, hw, E, count, sync, bn, training = ctx.meta
         H0, W0 = hw[0]
         dev = y0.device
-        dy = K.relu_bwd(dy.contiguous(), y)
-        st2, dgamma, dbeta = bn_grad_stats(y0, dy, mean, rstd, bn, sync)
-        dy0 = K.bn_bwd_apply(y0, dy, mean, rstd, gamma, st2, count)
+        dy0, dgamma, dbeta = bn_backward(dy, y0, (mean, rstd, count), gamma, bn, sync, training, relu_y=y)
         f32 = dict(device=dev, dtype=torch.float32)
         dbf = gslot(bf)
         if dbf is None:
@@ -788,11 +693,7 @@ class Conv3BNReLUFn(torch.autograd.Function):
         cols = K.conv3s1_im2col(x, shape)
         wp = K.conv3_weight_pack(w.detach(), dt, K.conv3s2_kp(cin))
         y0 = K.linear(cols, wp, b.detach())
-        count = y0.shape[0]
-        if bn.training:
-            mean, rstd, count = bn_batch_stats(y0, bn, sync)
-        else:
-            mean, rstd = bn.running_mean, torch.rsqrt(bn.running_var + bn.eps)
+        mean, rstd, count = bn_forward(y0, bn, sync)
         y = K.bn_apply(y0, mean, rstd, gamma, beta, act=2)
         ctx.save_for_backward(cols, wp, w, b, y0, y, mean, rstd, gamma)
         ctx.meta = (shape, cin, count, sync, bn, bn.training)
@@ -803,12 +704,7 @@ class Conv3BNReLUFn(torch.autograd.Function):
         K.TAG = "aux.bwd"
         cols, wp, w, b, y0, y, mean, rstd, gamma = ctx.saved_tensors
         shape, cin, count, sync, bn, training = ctx.meta
-        dy = K.relu_bwd(dy.contiguous(), y)
-        st2, dgamma, dbeta = bn_grad_stats(y0, dy, mean, rstd, bn, sync)
-        if training:
-            dy0 = K.bn_bwd_apply(y0, dy, mean, rstd, gamma, st2, count)
-        else:  # running statistics: BN is a fixed per-channel affine
-            dy0 = K.scale_mul(dy, colscale=rstd * gamma)
+        dy0, dgamma, dbeta = bn_backward(dy, y0, (mean, rstd, count), gamma, bn, sync, training, relu_y=y)
         dwp, db = K.linear_wgrad(dy0, cols, bias_grad=True, bias_out=gslot(b))
         dw = K.conv3_weight_unpack(dwp, cin, dw=gslot(w))
         dx = None
@@ -843,54 +739,10 @@ class FCNHead(nn.Module):
         conv, bn = self.conv[0], self.conv[1]
         y = Conv3BNReLUFn.apply(rows, (B, H, W), conv.weight, conv.bias, bn.weight, bn.bias, bn, self.syncbn)
         logits = LinearActFn.apply(y, self.classifier.weight, self.classifier.bias, 0, False)
-        return logits.view(B, H, W, self.num_classes).permute(0, 3, 1, 2)
+        return _logits_nchw(logits, B, (H, W))
 
 
 # ================================================================================== UPerNet head
-def _bn_forward(y0, bn, sync):
-    """(mean, rstd, count) of a BatchNorm over rows y0: batch statistics in train mode (running statistics
-    updated), the running statistics as a fixed affine in eval mode."""
-    if bn.training:
-        return bn_batch_stats(y0, bn, sync)
-    return bn.running_mean, torch.rsqrt(bn.running_var + bn.eps), y0.shape[0]
-
-
-def _bn_relu_backward(dy, y0, y, mean, rstd, gamma, bn, sync, count, training):
-    """dy0 of y = relu(BN(y0)) and the BN's (dgamma, dbeta)."""
-    dy = K.relu_bwd(dy.contiguous(), y)
-    st2, dgamma, dbeta = bn_grad_stats(y0, dy, mean, rstd, bn, sync)
-    if training:
-        dy0 = K.bn_bwd_apply(y0, dy, mean, rstd, gamma, st2, count)
-    else:  # running statistics: BN is a fixed per-channel affine
-        dy0 = K.scale_mul(dy, colscale=rstd * gamma)
-    return dy0, dgamma, dbeta
-
-
-class Conv1BiasBNReLUFn(torch.autograd.Function):
-    """y = relu(BN(x @ W^T + b)) — UPerHead's 1x1 Sequential(Conv2d(bias), BN, ReLU) (UPernet.py:38-42,
-    128-133). The bias sits ahead of a BatchNorm: in train mode it only enters running_mean and its
-    gradient is zero up to rounding; in eval mode it matters."""
-
-    @staticmethod
-    def forward(ctx, x, w, b, gamma, beta, bn, sync):
-        y0 = K.linear(x, wcast(x.dtype, w), b.detach())
-        mean, rstd, count = _bn_forward(y0, bn, sync)
-        y = K.bn_apply(y0, mean, rstd, gamma, beta, act=2)
-        ctx.save_for_backward(x, w, b, y0, y, mean, rstd, gamma)
-        ctx.meta = (count, sync, bn, bn.training)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        K.TAG = "decoder.bwd"
-        x, w, b, y0, y, mean, rstd, gamma = ctx.saved_tensors
-        count, sync, bn, training = ctx.meta
-        dy0, dgamma, dbeta = _bn_relu_backward(dy, y0, y, mean, rstd, gamma, bn, sync, count, training)
-        dW, db = K.linear_wgrad(dy0, x, out=gslot2(w), bias_grad=True, bias_out=gslot(b))
-        dx = K.linear_dgrad(dy0, wcast(x.dtype, w)) if ctx.needs_input_grad[0] else None
-        return dx, dW.view_as(w), db, dgamma, dbeta, None, None
-
-
 class Conv3IgemmBNReLUFn(torch.autograd.Function):
     """y = relu(BN(conv3x3(x) + b)) on NHWC rows with the implicit-GEMM conv (csrc/conv3_igemm.hip) —
     UPerHead's bottleneck, fpn_convs and fpn_bottleneck (UPernet.py:29-33, 43-47, 51-55). The gathered
@@ -901,7 +753,7 @@ class Conv3IgemmBNReLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, shape, w, b, gamma, beta, bn, sync):
         y0 = K.conv3_igemm(x, shape, wpack3(x.dtype, w), b.detach())
-        mean, rstd, count = _bn_forward(y0, bn, sync)
+        mean, rstd, count = bn_forward(y0, bn, sync)
         y = K.bn_apply(y0, mean, rstd, gamma, beta, act=2)
         ctx.save_for_backward(x, w, b, y0, y, mean, rstd, gamma)
         ctx.meta = (shape, count, sync, bn, bn.training)
@@ -912,7 +764,7 @@ class Conv3IgemmBNReLUFn(torch.autograd.Function):
         K.TAG = "decoder.bwd"
         x, w, b, y0, y, mean, rstd, gamma = ctx.saved_tensors
         shape, count, sync, bn, training = ctx.meta
-        dy0, dgamma, dbeta = _bn_relu_backward(dy, y0, y, mean, rstd, gamma, bn, sync, count, training)
+        dy0, dgamma, dbeta = bn_backward(dy, y0, (mean, rstd, count), gamma, bn, sync, training, relu_y=y)
         dwp, db = K.conv3_igemm_wgrad(dy0, x, shape, bias_grad=True, bias_out=gslot(b))
         dw = K.conv3_weight_unpack(dwp, x.shape[1], dw=gslot(w))
         dx = None
@@ -1034,7 +886,7 @@ class UPerHead(nn.Module):
 
     def _conv1(self, seq, x):
         conv, bn = seq[-3], seq[-2]
-        return Conv1BiasBNReLUFn.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn, self.syncbn)
+        return Conv1BNActFn.apply(x, None, conv.weight, conv.bias, bn.weight, bn.bias, bn, 2, self.syncbn)
 
     def _conv3(self, seq, x, shape):
         conv, bn = seq[0], seq[1]
@@ -1053,12 +905,8 @@ class UPerHead(nn.Module):
         return self._conv3(self.bottleneck, ResizeCatFn.apply(B, hw, *outs), shape)
 
     def forward(self, inputs):
-        rows, hw = [], []
         B = inputs[0].shape[0]
-        for f in inputs:
-            r, (b, h, w) = _nhwc_rows(f)
-            rows.append(r)
-            hw.append((h, w))
+        rows, hw = _rows_hw(inputs)
         n = len(rows)
         laterals = [self._conv1(seq, rows[i]) for i, seq in enumerate(self.lateral_convs)]
         laterals.append(self.psp_forward(rows[-1], (B,) + hw[-1]))
@@ -1066,10 +914,9 @@ class UPerHead(nn.Module):
             laterals[i - 1] = UpAddFn.apply(laterals[i - 1], laterals[i], B, hw[i - 1], hw[i])
         outs = [self._conv3(self.fpn_convs[i], laterals[i], (B,) + hw[i]) for i in range(n - 1)]
         outs.append(laterals[-1])
-        H, W = hw[0]
-        x = self._conv3(self.fpn_bottleneck, ResizeCatFn.apply(B, hw, *outs), (B, H, W))
+        x = self._conv3(self.fpn_bottleneck, ResizeCatFn.apply(B, hw, *outs), (B,) + hw[0])
         logits = LinearActFn.apply(x, self.conv_seg.weight, self.conv_seg.bias, 0, False)
-        return logits.view(B, H, W, self.num_classes).permute(0, 3, 1, 2)
+        return _logits_nchw(logits, B, hw[0])
 
 
 # ========================================================================================== loss

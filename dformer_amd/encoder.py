@@ -15,7 +15,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import kernels as K
-from .decoders import bn_batch_stats, bn_grad_stats, collectives_on
+from .batchnorm import bn_backward, bn_forward, collectives_on
 from .functional import ATTN_PARAM_NAMES, AttentionFn, ConvFFNFn, gslot, invalidate_weights, weights_epoch
 from .streams import fork, join, side_stream
 
@@ -190,13 +190,7 @@ class BNRowsFn(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, bn, sync):
         B, C, H, W = x.shape
         xr = x.permute(0, 2, 3, 1).contiguous().view(-1, C)
-        rows = xr.shape[0]
-        if bn.training:
-            mean, rstd, count = bn_batch_stats(xr, bn, sync)
-        else:
-            mean = bn.running_mean
-            rstd = torch.rsqrt(bn.running_var + bn.eps)
-            count = rows
+        mean, rstd, count = bn_forward(xr, bn, sync)
         y = K.bn_apply(xr, mean, rstd, gamma, beta)
         ctx.save_for_backward(xr, mean, rstd, gamma)
         ctx.sync, ctx.count, ctx.shape, ctx.bn = sync, count, (B, C, H, W), bn
@@ -209,11 +203,7 @@ class BNRowsFn(torch.autograd.Function):
         xr, mean, rstd, gamma = ctx.saved_tensors
         B, C, H, W = ctx.shape
         dyr = dy.permute(0, 2, 3, 1).contiguous().view(-1, C)
-        st2, dgamma, dbeta = bn_grad_stats(xr, dyr, mean, rstd, ctx.bn, ctx.sync)
-        if ctx.training:
-            dx = K.bn_bwd_apply(xr, dyr, mean, rstd, gamma, st2, ctx.count)
-        else:  # running statistics: BN is a fixed per-channel affine
-            dx = K.scale_mul(dyr, colscale=rstd * gamma)
+        dx, dgamma, dbeta = bn_backward(dyr, xr, (mean, rstd, ctx.count), gamma, ctx.bn, ctx.sync, ctx.training)
         return dx.view(B, H, W, C).permute(0, 3, 1, 2), dgamma, dbeta, None, None
 
 
@@ -237,12 +227,7 @@ class ConvS2Fn(torch.autograd.Function):
         xr = None
         if bn is not None:
             xr = x.permute(0, 2, 3, 1).reshape(B * H * W, C)  # the NHWC rows (a view for channels-last x)
-            if bn.training:
-                mean, rstd, count = bn_batch_stats(xr, bn, sync)
-            else:
-                mean = bn.running_mean
-                rstd = torch.rsqrt(bn.running_var + bn.eps)
-                count = xr.shape[0]
+            mean, rstd, count = bn_forward(xr, bn, sync)
             aff = (mean, rstd, bn_w.detach(), bn_b.detach())
         cols = K.conv3s2_im2col(x, dt, bn=aff, gelu=gelu)
         wp = K.conv3_weight_pack(weight.detach(), dt, kp)
@@ -273,13 +258,10 @@ class ConvS2Fn(torch.autograd.Function):
             dcols = K.linear_dgrad(dy, wp)
             mean, rstd, gamma, beta = aff
             dz = K.conv3s2_col2im(dcols, ctx.shape, cin, x=xr, bn=aff if ctx.gelu else None, gelu=ctx.gelu)
-            st2, dgamma, dbeta = bn_grad_stats(xr, dz, mean, rstd, ctx.bn, ctx.sync)
-            if ctx.needs_input_grad[0]:
+            dx, dgamma, dbeta = bn_backward(dz, xr, (mean, rstd, ctx.count), gamma, ctx.bn, ctx.sync, ctx.training,
+                                            need_dx=ctx.needs_input_grad[0])
+            if dx is not None:
                 B, H, W = ctx.shape
-                if ctx.training:
-                    dx = K.bn_bwd_apply(xr, dz, mean, rstd, gamma, st2, ctx.count)
-                else:  # running statistics: BN is a fixed per-channel affine
-                    dx = K.scale_mul(dz, colscale=rstd * gamma)
                 dx = dx.view(B, H, W, cin).permute(0, 3, 1, 2)
         return dx, dw, db, dgamma, dbeta, None, None, None, None
 

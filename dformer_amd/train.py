@@ -16,7 +16,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import kernels as K
-from .decoders import collectives_on
+from .batchnorm import collectives_on
 from .functional import invalidate_weights, register_grad_slot, register_shadow
 from .streams import join_streams
 
@@ -106,7 +106,7 @@ def fused_chains(model):
     """Parameter chains whose flat slots must be adjacent: each Attention's q | q_cut | l weights
     and biases (one GEMM in the forward, one weight-gradient GEMM in the backward), proj | proj_e,
     and every BatchNorm's bias | weight (the BN backward statistics (sum dy, sum dy * xhat) are
-    written straight into them, decoders.bn_grad_stats)."""
+    written straight into them, batchnorm.bn_grad_stats)."""
     chains = []
     for m in model.modules():
         if isinstance(m, nn.modules.batchnorm._BatchNorm) and m.affine:

@@ -76,14 +76,14 @@ def _run(rank, world, case):
     for m in frozen:
         m.eval()
     opt = FusedAdamW(model, lr=0.0, weight_decay=cfg.weight_decay, world=world, compute_dtype=torch.float32)
-    from dformer_amd import decoders
-    decoders.BN_PROBE = {}
+    from dformer_amd import batchnorm
+    batchnorm.BN_PROBE = {}
     try:
         loss = train_step(model, opt, rgb[sl].contiguous(), dep[sl].contiguous(), lab[sl].contiguous())
         torch.cuda.synchronize()
-        probe = decoders.BN_PROBE
+        probe = batchnorm.BN_PROBE
     finally:
-        decoders.BN_PROBE = None
+        batchnorm.BN_PROBE = None
     grads = [(gr.grad / world).cpu() for gr in opt.groups]
     bn_grads = {}
     for name, m in model.named_modules():

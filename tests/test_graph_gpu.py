@@ -95,7 +95,7 @@ def _free_port():
 
 
 def test_forced_collectives_one_rank_nccl():
-    """The world > 1 code on the GPU with one rank: a 1-rank RCCL group and decoders.FORCE_COLLECTIVES
+    """The world > 1 code on the GPU with one rank: a 1-rank RCCL group and batchnorm.FORCE_COLLECTIVES
     send every SyncBN statistic through all_gather_into_tensor + the device merge, every BN backward
     statistic, gradient bucket and the loss through all_reduce. A Tiny + ham step run that way eagerly
     and as a captured GraphedTrainStep must agree bit for bit, and both with the plain world-1 path
@@ -103,7 +103,7 @@ def test_forced_collectives_one_rank_nccl():
     utils/engine/engine.py:53-66 (the reference's DDP + SyncBN setup)."""
     import torch.distributed as dist
     import bench
-    from dformer_amd import decoders as D
+    from dformer_amd import batchnorm as D
     from dformer_amd.segmentor import EncoderDecoder
     from dformer_amd.train import FusedAdamW, GraphedTrainStep, train_step
     dev = torch.device("cuda", 0)
