@@ -1,4 +1,4 @@
-"""Shared by tests/test_fss_*.py and tools/make_fss_goldens.py: deterministic episode masks and a torch float64
+"""Shared by tests/test_fss_*.py and oracle/golden_e2e.py: deterministic episode masks and a torch float64
 restatement of the few-shot tail of meta_forward (models/builder.py:273-308) in its collapsed form
 (DESIGN.md §6e). Nothing here touches the package under test or the reference."""
 import numpy as np

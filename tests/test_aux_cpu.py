@@ -1,6 +1,6 @@
 """The auxiliary FCN head (fcnhead.py:9-29, builder.py:138-143) on the host: which configs build it, its
 state-dict keys / child order / optimizer groups against the reference's (tests/golden/e2e_tiny_aux*.npz,
-tools/make_aux_goldens.py), checkpoint loading, and the argument validation of its two conv entry points."""
+oracle/golden_decoders.py / golden_e2e.py), checkpoint loading, and the argument validation of its two conv entry points."""
 import ctypes
 
 import numpy as np

@@ -1,6 +1,6 @@
 """The auxiliary FCN head on the GPU (fcnhead.py:9-29, builder.py:138-143, 204-207, 231-232): the dense 3x3
 stride-1 gather / col2im kernels against torch, FCNHead against the reference's fp64 goldens
-(tools/make_aux_goldens.py), the fused loss at the aux head's x16 / non-integer factors, the training forward
+(oracle/golden_decoders.py / golden_e2e.py), the fused loss at the aux head's x16 / non-integer factors, the training forward
 with aux_rate = 0.4 end to end, eval parity with a model without the head, and the optimizer / HIP-graph
 plumbing."""
 import numpy as np

@@ -81,7 +81,7 @@ def fp32_golden_check(g, blk, x, xe, y, ye, last):
 
 
 # bf16 gates relative to the reference's OWN bf16 error on the same Block (tests/golden/bf16env_block_*,
-# oracle/make_goldens.py golden_block_bf16_env: reference float32 under torch.autocast(bfloat16) vs
+# oracle/golden_blocks.py golden_block_bf16_env: reference float32 under torch.autocast(bfloat16) vs
 # its fp64 golden, per output and per parameter gradient). The HIP path stores every activation in
 # bf16 (autocast keeps LN / GELU / elementwise results in fp32), so each error may be up to
 # BF16_ENV_MULT times the envelope, the envelope floored at one bf16 rounding (2^-8): gates that

@@ -166,7 +166,7 @@ def test_evaluate_msf_vs_oracle(arch, dec, ncls):
                                                       ("msf_tiny_mlp", "DFormer-Tiny", "MLPDecoder", 37, 64)])
 def test_evaluate_msf_vs_reference_golden(name, arch, dec, ncls, embed):
     """The HIP evaluate_msf against the reference's own evaluate_msf (utils/val_mm.py:325-472, run by
-    oracle/make_goldens.py golden_msf over two batches): the summed softmax scores of every batch at
+    oracle/golden_eval.py golden_msf over two batches): the summed softmax scores of every batch at
     1e-3 (fp32) and the confusion histogram (argmax near-ties may flip a handful of pixels)."""
     from goldens import load
     from dformer_amd.evaluate import evaluate_msf, msf_scores

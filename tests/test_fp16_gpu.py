@@ -4,7 +4,7 @@ fp16 storage, fp32 accumulation / LN / BN / softmax statistics, dynamic loss sca
 
 Gates: per Block vs the fp64 reference goldens at Large's stage geometries (incl. the 530x730
 run's 34x46 stage-2 and 17x23 stage-3 planes); end to end vs the reference's OWN fp16 autocast
-error on the same golden (tests/golden/f16env_*.npz, oracle/make_goldens.py golden_bf16_env with
+error on the same golden (tests/golden/f16env_*.npz, oracle/golden_e2e.py golden_e2e_env with
 dtype=float16); the training step with the loss scaler."""
 import numpy as np
 import pytest

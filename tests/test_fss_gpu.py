@@ -1,6 +1,6 @@
 """Few-shot episodes on the GPU (models/builder.py:237-320): the fss kernels against float64 (autograd of
 F.interpolate, F.cosine_similarity and F.cross_entropy on the CPU, and the collapsed restatement of
-fss_common), meta_forward against the reference's float64 golden (tools/make_fss_goldens.py), the eager
+fss_common), meta_forward against the reference's float64 golden (oracle/golden_e2e.py), the eager
 episode training step and fss_evaluate.
 
 Tolerances, the rule of tests/test_trav_gpu.py: rel-to-max within max(1e-4, 10 x the reference's own float32

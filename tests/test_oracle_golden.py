@@ -70,7 +70,7 @@ def test_ham_head_golden():
     name = "ham_tiny"
     g = load(name)
     B, H, W, ncls, train, seed, *in_ch = [int(v) for v in g["meta"]]
-    tag = f"{name}#{seed}"  # the input draw whose ReLU inputs stay off the kink (make_goldens.golden_ham)
+    tag = f"{name}#{seed}"  # the input draw whose ReLU inputs stay off the kink (golden_decoders.golden_ham)
     p = params(R.ham_shapes(in_ch, ncls, pre=""))
     feats = [torch.from_numpy(gen.normal(tag + f"/f{i}", (B, c, H >> i, W >> i))).requires_grad_()
              for i, c in enumerate(in_ch)]
@@ -173,7 +173,7 @@ def test_optimizer_groups_golden():
                                                       ("msf_tiny_mlp", "DFormer-Tiny", "MLPDecoder", 37, 64)])
 def test_msf_golden(name, arch, dec, ncls, embed):
     """The oracle's evaluate_msf restatement (msf_scores, confusion) against the reference's own
-    evaluate_msf run (utils/val_mm.py:325-472; oracle/make_goldens.py golden_msf)."""
+    evaluate_msf run (utils/val_mm.py:325-472; oracle/golden_eval.py golden_msf)."""
     g = load(name)
     B, H, W, _, flip = [int(v) for v in g["meta"]]
     scales = [float(s) for s in g["scales"]]

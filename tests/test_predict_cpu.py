@@ -1,6 +1,6 @@
 """Single-scale evaluation and prediction export, the parts that need no GPU: argument validation of
 dfm_seg_predict / dfm_rows_argmax, the declarations, the host-side naming and palette helpers, and the
-self-consistency of the reference fixtures (tools/make_eval_goldens.py)."""
+self-consistency of the reference fixtures (oracle/golden_eval.py)."""
 import ctypes
 import os
 import re

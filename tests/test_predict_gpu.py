@@ -1,6 +1,6 @@
 """Single-scale evaluation on the HIP path: dfm_seg_predict / dfm_rows_argmax against torch, and
 dformer_amd.evaluate.evaluate / save_preds / EncoderDecoder.predict against the reference's own
-evaluate (utils/val_mm.py:102-207; tests/golden/eval_*.npz from tools/make_eval_goldens.py)."""
+evaluate (utils/val_mm.py:102-207; tests/golden/eval_*.npz from oracle/golden_eval.py)."""
 import functools
 import os
 
@@ -210,7 +210,7 @@ def test_evaluate_vs_reference_golden(name, dec, ncls, embed):
     model.predict may differ from the reference's argmax only where the float64 top-2 gap is within
     2e-3 of max |logit| (the project's fp32 gate is 1e-3 of max per logit, and two logits can move), at
     most max(2, 1e-3 * npix) pixels may, and the histogram gets test_eval_gpu.py's allowance.
-    Share of pixels inside the band (tools/make_eval_goldens.py): eval_tiny_ham 58 of 14000 (0.41%),
+    Share of pixels inside the band (oracle/golden_eval.py): eval_tiny_ham 58 of 14000 (0.41%),
     eval_tiny_mlp 226 of 14000 (1.61%)."""
     from dformer_amd.evaluate import evaluate
     g = load(name)

@@ -79,7 +79,7 @@ def test_segmentor_fp32_vs_reference(name, arch, dec, ncls):
 
 
 # fp32 end-to-end gates, from the reference's OWN float32 error on each golden (tests/golden/
-# fp32env_*.npz: the reference run in float32 vs its float64 golden, oracle/make_goldens.py
+# fp32env_*.npz: the reference run in float32 vs its float64 golden, oracle/golden_e2e.py golden_e2e_env
 # golden_bf16_env(dtype=None)): 10 x that envelope, floored at 1e-4 — ten times tighter than
 # SURVEY §8c's 1e-3 fp32 gate wherever the envelope allows (it allows it everywhere but for the
 # mathematically-zero gradients of conv biases ahead of a train-mode BatchNorm, whose fingerprints
@@ -178,7 +178,7 @@ def test_nmf2d_vs_reference(train):
 @pytest.mark.gpu
 def test_ham_head_vs_reference():
     """LightHamHead fwd + bwd vs the reference (fp64 golden) at 1e-3. The golden's inputs were drawn
-    (oracle/make_goldens.py golden_ham) so that every ReLU input is >= 1e-5 x max away from the
+    (oracle/golden_decoders.py golden_ham) so that every ReLU input is >= 1e-5 x max away from the
     kink: the fp32 HIP path then takes the same activation pattern as fp64 everywhere."""
     from dformer_amd.decoders import LightHamHead
     name = "ham_tiny"
@@ -283,7 +283,7 @@ def test_tiny_full_480x640_fp32_vs_reference():
 
 
 # bf16 end-to-end gates, relative to the reference's OWN bf16 autocast error on the same golden
-# (tests/golden/bf16env_*.npz, oracle/make_goldens.py golden_bf16_env; SURVEY §8c: the reference's
+# (tests/golden/bf16env_*.npz, oracle/golden_e2e.py golden_e2e_env; SURVEY §8c: the reference's
 # autocast misses a flat 1e-2 logits gate by itself — 1.0-2.1e-2 on these goldens and 2.2e-2 on the
 # SURVEY's Tiny probe — and lands at a median 2-7e-2 on the parameter-gradient fingerprints).
 # bf16 end-to-end error is chaotic in the accumulation order: on MI355X the same model run with the

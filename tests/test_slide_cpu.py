@@ -12,7 +12,7 @@ from goldens import load
 @pytest.mark.parametrize("name", ["slide_tiny_ham", "slide_tiny_mlp"])
 def test_slide_windows_match_reference(name):
     """slide_windows on the size each scale was cut from equals the windows the reference padded its crop
-    logits back into (tools/make_slide_goldens.py), per scale and axis."""
+    logits back into (oracle/golden_eval.py), per scale and axis."""
     from dformer_amd.evaluate import msf_size, slide_strides, slide_windows
     g = load(name)
     _, H, W, _, _ = [int(v) for v in g["meta"]]

@@ -1,7 +1,7 @@
 """Sliding-window multi-scale evaluation on the GPU (csrc/eval.hip dfm_slide_msf_accumulate,
 dformer_amd.evaluate): the kernel against a torch restatement of utils/val_mm.py:257-322 + 377-397,
 slide_inference against the same restatement around the model's own encode_decode, and msf_scores /
-evaluate_msf with sliding windows against the reference's own run (tools/make_slide_goldens.py)."""
+evaluate_msf with sliding windows against the reference's own run (oracle/golden_eval.py)."""
 import functools
 
 import numpy as np

@@ -1,5 +1,5 @@
 """The DFormerTrav backbone on the host (DFormer.py:308-457, builder.py:109-111): the algebra of the collapsed
-laser-scan expansion against the reference's float64 goldens (tools/make_trav_goldens.py), the state-dict keys,
+laser-scan expansion against the reference's float64 goldens (oracle/golden_e2e.py), the state-dict keys,
 child order and optimizer groups against the reference's, checkpoint loading, and the argument validation of
 the two laser entry points."""
 import ctypes

@@ -1,6 +1,6 @@
 """The DFormerTrav backbone on the GPU (DFormer.py:308-457): the two laser-expansion kernels against the
 float64 collapse (trav_common), Attention1Dto2D and the whole model against the reference's float64 goldens
-(tools/make_trav_goldens.py), the depth stem's Cin = 1 input gradient, the optimizer / HIP-graph plumbing and
+(oracle/golden_e2e.py), the depth stem's Cin = 1 input gradient, the optimizer / HIP-graph plumbing and
 the evaluation surface with a scan as modal_x.
 
 Tolerances: rel-to-max within max(1e-4, 10 x the reference's own float32 error stored in env/), the rule of

@@ -1,6 +1,6 @@
 """The UPerNet decoder (UPernet.py:8-146, builder.py:145-152) on the host: the new entry points resolve and
 validate their arguments before touching a device, `decoder="UPernet"` builds, and its state-dict keys / shapes
-and optimizer groups equal the reference's in order (tests/golden/e2e_tiny_uper.npz, tools/make_uper_goldens.py)."""
+and optimizer groups equal the reference's in order (tests/golden/e2e_tiny_uper.npz, oracle/golden_decoders.py / golden_e2e.py)."""
 import ctypes
 import os
 import re

@@ -1,6 +1,6 @@
 """The UPerNet decoder on the GPU (UPernet.py:8-146, builder.py:145-152): the implicit-GEMM 3x3 conv (forward,
 input gradient, weight gradient) and the pyramid pooling against torch in fp64, UPerHead against the
-reference's fp64 goldens (tools/make_uper_goldens.py), DFormer-Tiny + UPernet end to end, eval parity and the
+reference's fp64 goldens (oracle/golden_decoders.py / golden_e2e.py), DFormer-Tiny + UPernet end to end, eval parity and the
 optimizer / HIP-graph plumbing."""
 import copy
 import functools

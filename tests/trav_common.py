@@ -1,4 +1,4 @@
-"""Shared by tests/test_trav_*.py and tools/make_trav_goldens.py: deterministic values for the DFormerTrav
+"""Shared by tests/test_trav_*.py and oracle/golden_e2e.py: deterministic values for the DFormerTrav
 keys gen.param_value does not know (query1 / query2 / in_proj_*), the scans, and a torch float64
 restatement of what Attention1Dto2D (DFormer.py:308-339) computes once it is collapsed.
 Nothing here touches the package under test or the reference."""
