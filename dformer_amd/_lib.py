@@ -188,6 +188,15 @@ _SIGS = {
     "dfm_seg_loss_grad_partials_size": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "dfm_seg_loss_fwd_grad": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P, P, P]),
     "dfm_seg_loss_bwd_gather": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "dfm_seg_loss_opts_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P, c_float, P, P,
+                                      P]),
+    "dfm_seg_loss_opts_fwd_grad": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P, c_float,
+                                           P, P, P]),
+    "dfm_seg_loss_opts_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, P, c_float, P, P,
+                                      P, P, P]),
+    "dfm_seg_loss_ohem_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "dfm_seg_loss_ohem_relabel": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, c_float,
+                                          c_long, P, P, P, P, P]),
     "dfm_fss_footprint_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "dfm_fss_mask_footprint": (c_int, [c_int, c_int, c_int, c_int, c_int, P, P, P, P, P]),
     "dfm_fss_proto_pool_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_long, P, P, P, P, P]),

@@ -15,6 +15,34 @@
 namespace {
 constexpr int MAXC = 64;
 
+// Criterion options of nn.CrossEntropyLoss (builder.py:230 with weight= / label_smoothing=): per pixel
+//   l = (1 - eps) w[y] (lse - z_y) + eps / C sum_c w[c] (lse - z_c)
+//     = w_eff lse - (1 - eps) w[y] z_y - eps / C sum_c w[c] z_c,   w_eff = (1 - eps) w[y] + eps / C sum_c w[c]
+//   dl / dz_c = w_eff p_c - [(1 - eps) w[y] delta_cy + eps / C w[c]]
+// The mean stays over the valid-pixel count (reduction='none' followed by [valid].mean()), not the
+// weight sum. Every loss kernel takes OPT as a compile-time switch: OPT = false is the plain criterion
+// and compiles to what it was before the options existed (no weight staging, no extra registers).
+struct ClsOpts {
+  const float* w;  // [ncls] class weights, NULL = all 1
+  float eps;       // label smoothing
+};
+constexpr int SW_SUM = MAXC;  // sw[SW_SUM] = sum_c w[c]
+
+// w[] -> LDS once per block (sw[c] = 0 for c >= ncls), the weight sum in a fixed order
+template <bool OPT>
+DFM_INLINE void stage_weights(float* sw, const ClsOpts& o, int ncls) {
+  if constexpr (OPT) {
+    if (threadIdx.x < MAXC) sw[threadIdx.x] = (int)threadIdx.x < ncls ? (o.w ? o.w[threadIdx.x] : 1.f) : 0.f;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float t = 0.f;
+      for (int c = 0; c < ncls; ++c) t += sw[c];
+      sw[SW_SUM] = t;
+    }
+    __syncthreads();
+  }
+}
+
 DFM_INLINE void src_idx(int dst, int in, int out, int& i0, int& i1, float& l1) {
   const float scale = (float)in / (float)out;
   float src = scale * (dst + 0.5f) - 0.5f;
@@ -63,23 +91,27 @@ DFM_INLINE void interp(const T* lg, int b, int h, int w, int ncls, int y, int x,
     z[c] = c < ncls ? a00 * ldf(p00 + c) + a01 * ldf(p01 + c) + a10 * ldf(p10 + c) + a11 * ldf(p11 + c) : -INFINITY;
 }
 
-template <typename T, int NC>
+template <typename T, int NC, bool OPT>
 __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(int B, int h, int w, int ncls, const T* __restrict__ lg,
                                                            int H, int W, const long* __restrict__ label, int ignore,
-                                                           float* __restrict__ lse_out, float* __restrict__ part) {
+                                                           float* __restrict__ lse_out, float* __restrict__ part,
+                                                           ClsOpts o) {
   const long n = (long)B * H * W;
   const bool vec = ncls % 8 == 0 && ((uintptr_t)lg & 15) == 0;
+  __shared__ float sw[OPT ? MAXC + 1 : 1];
+  stage_weights<OPT>(sw, o, ncls);
   float s = 0.f, cnt = 0.f;
   for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < n; p += (long)gridDim.x * blockDim.x) {
     const int x = p % W, y = (p / W) % H, b = p / ((long)W * H);
     const long lab = label[p];
     float z[NC];
     interp(lg, b, h, w, ncls, y, x, H, W, z, vec);
-    float m = -INFINITY, zl = 0.f;
+    float m = -INFINITY, zl = 0.f, swz = 0.f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       m = fmaxf(m, z[c]);
       zl = (c == lab) ? z[c] : zl;
+      if constexpr (OPT) swz += c < ncls ? sw[c] * z[c] : 0.f;
     }
     float se = 0.f;
 #pragma unroll
@@ -87,7 +119,12 @@ __global__ __launch_bounds__(256) void seg_loss_fwd_kernel(int B, int h, int w, 
     const float lse = m + __logf(se);
     if (lse_out) lse_out[p] = lse;
     if (lab != ignore && lab >= 0 && lab < ncls) {
-      s += lse - zl;
+      if constexpr (OPT) {
+        const float epsC = o.eps / (float)ncls, wy = (1.f - o.eps) * sw[lab];
+        s += (wy + epsC * sw[SW_SUM]) * lse - wy * zl - epsC * swz;
+      } else {
+        s += lse - zl;
+      }
       cnt += 1.f;
     }
   }
@@ -140,14 +177,16 @@ DFM_INLINE int first_pixel(int j, int in, int out) {
   return max(0, (int)floorf(((float)j + 0.5f) * inv - 0.5f) - 2);
 }
 
-template <typename T, int NC>
+template <typename T, int NC, bool OPT>
 __global__ __launch_bounds__(XP_NT) void seg_loss_bwd_xpass_kernel(int B, int h, int w, int ncls,
                                                                     const T* __restrict__ lg, int H, int W,
                                                                     const long* __restrict__ label, int ignore,
                                                                     const float* __restrict__ loss_out,
                                                                     const float* __restrict__ gscale,
-                                                                    float* __restrict__ rx, int RY, int PJ) {
+                                                                    float* __restrict__ rx, int RY, int PJ, ClsOpts o) {
   extern __shared__ __attribute__((aligned(16))) float res[];  // [XP_NT][ncls + 1]
+  __shared__ float sw[OPT ? MAXC + 1 : 1];
+  stage_weights<OPT>(sw, o, ncls);
   const int GLD = ncls + 1, PX = XP_NT / RY;
   const int nj = (w + PJ - 1) / PJ, ny = (H + RY - 1) / RY;
   int bid = blockIdx.x;
@@ -188,10 +227,24 @@ __global__ __launch_bounds__(XP_NT) void seg_loss_bwd_xpass_kernel(int B, int h,
         z[c] = c < ncls ? __expf(z[c] - m) : 0.f;
         se += z[c];
       }
-      const float rs = inv / se;
+      if constexpr (OPT) {
+        // one fused multiply-add per class, as the plain form below compiles to: neutral options
+        // (w = 1, eps = 0) then give its bits
+        const float epsC = o.eps / (float)ncls, wy = (1.f - o.eps) * sw[lab];
+        const float rs = inv / se * (wy + epsC * sw[SW_SUM]);
+        const float iy = inv * wy, ie = inv * epsC;
 #pragma unroll
-      for (int c = 0; c < NC; ++c)
-        if (c < ncls) row[c] = z[c] * rs - (c == lab ? inv : 0.f);
+        for (int c = 0; c < NC; ++c)
+          if (c < ncls) {
+            const float sub = (c == lab ? iy : 0.f) + ie * sw[c];
+            row[c] = fmaf(z[c], rs, -sub);
+          }
+      } else {
+        const float rs = inv / se;
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          if (c < ncls) row[c] = z[c] * rs - (c == lab ? inv : 0.f);
+      }
     } else {
       for (int c = 0; c < ncls; ++c) row[c] = 0.f;
     }
@@ -268,15 +321,17 @@ bool xpass_shape(int w, int W, int& RY, int& PJ) {
 // low-res cell, the 4 corner partials that touch it in a fixed order: deterministic, no atomics.
 constexpr int TILE_NT = 128;  // 2 waves; res[] stays under 64 KB of static LDS at MAXC
 
-template <typename T, int S>
+template <typename T, int S, bool OPT>
 __global__ __launch_bounds__(TILE_NT) void seg_loss_bwd_tile_kernel(int B, int h, int w, int ncls,
                                                                     const T* __restrict__ lg, int H, int W,
                                                                     const long* __restrict__ label, int ignore,
                                                                     const float* __restrict__ loss_out,
                                                                     const float* __restrict__ gscale,
-                                                                    float* __restrict__ part, long ntiles) {
+                                                                    float* __restrict__ part, long ntiles, ClsOpts o) {
   constexpr int TP = S * S, TPW = 64 / TP;   // pixels per tile, tiles per wave
   constexpr int RP = MAXC + 1;               // LDS row pitch of a pixel's residual
+  __shared__ float sw[OPT ? MAXC + 1 : 1];
+  stage_weights<OPT>(sw, o, ncls);
   __shared__ float res[TILE_NT][RP];
   __shared__ float wts[TILE_NT][4];          // per pixel: weights of corner slots (y0 x0, y0 x1, y1 x0, y1 x1)
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -304,10 +359,24 @@ __global__ __launch_bounds__(TILE_NT) void seg_loss_bwd_tile_kernel(int B, int h
         z[c] = c < ncls ? __expf(z[c] - m) : 0.f;
         se += z[c];
       }
-      const float rs = inv / se;
+      if constexpr (OPT) {
+        // one fused multiply-add per class, as the plain form below compiles to: neutral options
+        // (w = 1, eps = 0) then give its bits
+        const float epsC = o.eps / (float)ncls, wy = (1.f - o.eps) * sw[lab];
+        const float rs = inv / se * (wy + epsC * sw[SW_SUM]);
+        const float iy = inv * wy, ie = inv * epsC;
 #pragma unroll
-      for (int c = 0; c < MAXC; ++c)
-        if (c < ncls) row[c] = z[c] * rs - (c == lab ? inv : 0.f);
+        for (int c = 0; c < MAXC; ++c)
+          if (c < ncls) {
+            const float sub = (c == lab ? iy : 0.f) + ie * sw[c];
+            row[c] = fmaf(z[c], rs, -sub);
+          }
+      } else {
+        const float rs = inv / se;
+#pragma unroll
+        for (int c = 0; c < MAXC; ++c)
+          if (c < ncls) row[c] = z[c] * rs - (c == lab ? inv : 0.f);
+      }
       int a0, a1, b0, b1;
       float ly, lx;
       src_idx(y, h, H, a0, a1, ly);
@@ -370,18 +439,21 @@ __global__ void seg_loss_gather_kernel(int B, int h, int w, int ncls, const floa
 // L2 per pixel) and the loss terms reduced per block. The residual (softmax - onehot) and the corner
 // partials are left unscaled; seg_loss_gather_scaled_kernel applies gscale / count once the count is
 // known (the backward then costs one gather).
-template <typename T, int S, int NC>
+template <typename T, int S, int NC, bool OPT>
 __global__ __launch_bounds__(TILE_NT) void seg_loss_fused_tile_kernel(int B, int h, int w, int ncls,
                                                                       const T* __restrict__ lg, int H, int W,
                                                                       const long* __restrict__ label, int ignore,
                                                                       float* __restrict__ part,
-                                                                      float* __restrict__ lpart, long ntiles) {
+                                                                      float* __restrict__ lpart, long ntiles,
+                                                                      ClsOpts o) {
   constexpr int TP = S * S, TPW = 64 / TP;
   constexpr int RP = NC + 1;  // NC >= ncls: class registers / LDS rows sized for the class count
   __shared__ float res[TILE_NT][RP];
   __shared__ float wts[TILE_NT][4];
   __shared__ float corner[TILE_NT / 64][TPW][4][NC];
   __shared__ float lred[2][TILE_NT / 64];
+  __shared__ float sw[OPT ? MAXC + 1 : 1];
+  stage_weights<OPT>(sw, o, ncls);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const long tile0 = ((long)blockIdx.x * (TILE_NT / 64) + wid) * TPW;
   const int tw = w + 1, th = h + 1;
@@ -419,7 +491,7 @@ __global__ __launch_bounds__(TILE_NT) void seg_loss_fused_tile_kernel(int B, int
                            (b0 == tx ? 1.f - lx : 0.f) + (b1 == tx ? lx : 0.f)};
       wv[0] = wy[0] * wx[0]; wv[1] = wy[0] * wx[1]; wv[2] = wy[1] * wx[0]; wv[3] = wy[1] * wx[1];
       float z[NC];
-      float m = -INFINITY, zl = 0.f;
+      float m = -INFINITY, zl = 0.f, swz = 0.f;
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
         if (c < ncls) {
@@ -427,6 +499,7 @@ __global__ __launch_bounds__(TILE_NT) void seg_loss_fused_tile_kernel(int B, int
                  wv[3] * corner[wid][tt][3][c];
           m = fmaxf(m, z[c]);
           zl = c == lab ? z[c] : zl;
+          if constexpr (OPT) swz += sw[c] * z[c];
         }
       }
       float se = 0.f;
@@ -436,12 +509,25 @@ __global__ __launch_bounds__(TILE_NT) void seg_loss_fused_tile_kernel(int B, int
           z[c] = __expf(z[c] - m);
           se += z[c];
         }
-      ls = m + __logf(se) - zl;
       lc = 1.f;
-      const float rs = 1.f / se;
+      if constexpr (OPT) {
+        const float epsC = o.eps / (float)ncls, wy = (1.f - o.eps) * sw[lab];
+        const float weff = wy + epsC * sw[SW_SUM];
+        ls = weff * (m + __logf(se)) - wy * zl - epsC * swz;
+        const float rs = 1.f / se * weff;
 #pragma unroll
-      for (int c = 0; c < NC; ++c)
-        if (c < ncls) row[c] = z[c] * rs - (c == lab ? 1.f : 0.f);
+        for (int c = 0; c < NC; ++c)
+          if (c < ncls) {
+            const float sub = (c == lab ? wy : 0.f) + epsC * sw[c];
+            row[c] = fmaf(z[c], rs, -sub);  // fused, as in seg_loss_bwd_tile_kernel
+          }
+      } else {
+        ls = m + __logf(se) - zl;
+        const float rs = 1.f / se;
+#pragma unroll
+        for (int c = 0; c < NC; ++c)
+          if (c < ncls) row[c] = z[c] * rs - (c == lab ? 1.f : 0.f);
+      }
     } else {
       for (int c = 0; c < ncls; ++c) row[c] = 0.f;
     }
@@ -531,9 +617,9 @@ __global__ void seg_loss_gather_scaled_kernel(int B, int h, int w, int ncls, con
   }
 }
 
-template <typename T>
+template <typename T, bool OPT>
 int launch_fused_tiles(int S, int B, int h, int w, int ncls, const void* lg, int H, int W, const long* label,
-                       int ignore, float* loss_out, float* part, float* lpart, hipStream_t s) {
+                       int ignore, float* loss_out, float* part, float* lpart, ClsOpts o, hipStream_t s) {
   const long ntiles = (long)B * (h + 1) * (w + 1);
   const long tiles_per_block = (TILE_NT / 64) * (64 / (S * S));
   const unsigned nb = cdiv(ntiles, tiles_per_block);
@@ -541,8 +627,8 @@ int launch_fused_tiles(int S, int B, int h, int w, int ncls, const void* lg, int
   // 2 waves per SIMD (VGPRs and the residual rows in LDS), the 40-wide one 3 (461.8-462.1 ->
   // 464.4-464.5 images/s A/B)
 #define SEG_GO(SS, NCC)                                                                                        \
-  DFM_LAUNCH((seg_loss_fused_tile_kernel<T, SS, NCC>), dim3(nb), dim3(TILE_NT), 0, s, B, h, w, ncls, (const T*)lg, \
-             H, W, label, ignore, part, lpart, ntiles)
+  DFM_LAUNCH((seg_loss_fused_tile_kernel<T, SS, NCC, OPT>), dim3(nb), dim3(TILE_NT), 0, s, B, h, w, ncls,         \
+             (const T*)lg, H, W, label, ignore, part, lpart, ntiles, o)
   if (S == 8) {
     if (ncls <= 40) SEG_GO(8, 40);
     else SEG_GO(8, MAXC);
@@ -557,22 +643,22 @@ int launch_fused_tiles(int S, int B, int h, int w, int ncls, const void* lg, int
   return DFM_OK;
 }
 
-template <typename T>
+template <typename T, bool OPT>
 int launch_bwd_tiles(int S, int B, int h, int w, int ncls, const void* lg, int H, int W, const long* label,
-                     int ignore, const float* loss_out, const float* gscale, float* part, float* dlg,
+                     int ignore, const float* loss_out, const float* gscale, float* part, float* dlg, ClsOpts o,
                      hipStream_t s) {
   const long ntiles = (long)B * (h + 1) * (w + 1);
   const long tiles_per_block = (TILE_NT / 64) * (64 / (S * S));
   const unsigned nb = cdiv(ntiles, tiles_per_block);
   if (S == 8)
-    DFM_LAUNCH((seg_loss_bwd_tile_kernel<T, 8>), dim3(nb), dim3(TILE_NT), 0, s, B, h, w, ncls, (const T*)lg, H, W,
-               label, ignore, loss_out, gscale, part, ntiles);
+    DFM_LAUNCH((seg_loss_bwd_tile_kernel<T, 8, OPT>), dim3(nb), dim3(TILE_NT), 0, s, B, h, w, ncls, (const T*)lg, H,
+               W, label, ignore, loss_out, gscale, part, ntiles, o);
   else if (S == 4)
-    DFM_LAUNCH((seg_loss_bwd_tile_kernel<T, 4>), dim3(nb), dim3(TILE_NT), 0, s, B, h, w, ncls, (const T*)lg, H, W,
-               label, ignore, loss_out, gscale, part, ntiles);
+    DFM_LAUNCH((seg_loss_bwd_tile_kernel<T, 4, OPT>), dim3(nb), dim3(TILE_NT), 0, s, B, h, w, ncls, (const T*)lg, H,
+               W, label, ignore, loss_out, gscale, part, ntiles, o);
   else
-    DFM_LAUNCH((seg_loss_bwd_tile_kernel<T, 2>), dim3(nb), dim3(TILE_NT), 0, s, B, h, w, ncls, (const T*)lg, H, W,
-               label, ignore, loss_out, gscale, part, ntiles);
+    DFM_LAUNCH((seg_loss_bwd_tile_kernel<T, 2, OPT>), dim3(nb), dim3(TILE_NT), 0, s, B, h, w, ncls, (const T*)lg, H,
+               W, label, ignore, loss_out, gscale, part, ntiles, o);
   DFM_LAUNCH_CHECK();
   const long n = (long)B * h * w * ncls;
   DFM_LAUNCH(seg_loss_gather_kernel, dim3(min(8192L, (n + 255) / 256)), dim3(256), 0, s, B, h, w, ncls,
@@ -602,18 +688,20 @@ extern "C" size_t dfm_seg_loss_bwd_workspace(int B, int h, int w, int ncls, int 
   return (size_t)B * H * w * ncls * sizeof(float);
 }
 
-extern "C" int dfm_seg_loss_fwd(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
-                                const long* label, int ignore, float* lse, float* loss_out, void* workspace,
-                                dfm_stream_t stream) {
-  DFM_CHECK_DTYPE(dtype);
-  DFM_CHECK_ARG(logits && label && loss_out && workspace && ncls <= MAXC, "dfm_seg_loss_fwd: bad argument");
-  hipStream_t s = (hipStream_t)stream;
+// The four loss paths, once for the plain criterion (OPT = false: the public entry points below, the
+// kernels they always launched) and once with class weights / label smoothing (dfm_seg_loss_opts_*).
+// fn is the entry point's name for its messages; the dtype code was checked by the caller.
+template <bool OPT>
+static int seg_loss_fwd_impl(const char* fn, int dtype, int B, int h, int w, int ncls, const void* logits, int H,
+                             int W, const long* label, int ignore, float* lse, float* loss_out, void* workspace,
+                             ClsOpts o, hipStream_t s) {
+  DFM_CHECK_ARG(logits && label && loss_out && workspace && ncls <= MAXC, "%s: bad argument", fn);
   const long n = (long)B * H * W;
   const int nblk = (int)min((long)LOSS_BLOCKS, (n + 255) / 256);
   DFM_DTYPE_SWITCH(dtype, T,
-                   DFM_LAUNCH((ncls <= 40 ? seg_loss_fwd_kernel<T, 40> : seg_loss_fwd_kernel<T, MAXC>), dim3(nblk),
-                              dim3(256), 0, s, B, h, w, ncls, (const T*)logits, H, W, label, ignore, lse,
-                              (float*)workspace));
+                   DFM_LAUNCH((ncls <= 40 ? seg_loss_fwd_kernel<T, 40, OPT> : seg_loss_fwd_kernel<T, MAXC, OPT>),
+                              dim3(nblk), dim3(256), 0, s, B, h, w, ncls, (const T*)logits, H, W, label, ignore, lse,
+                              (float*)workspace, o));
   DFM_LAUNCH_CHECK();
   DFM_LAUNCH(seg_loss_sum_kernel, dim3(1), dim3(64), 0, s, nblk, (const float*)workspace, loss_out);
   DFM_LAUNCH_CHECK();
@@ -623,6 +711,62 @@ extern "C" int dfm_seg_loss_fwd(int dtype, int B, int h, int w, int ncls, const 
 static int fused_scale(int h, int w, int H, int W) {
   const int S = tile_scale(h, w, H, W);
   return S == 8 || S == 4 ? S : 0;
+}
+
+template <bool OPT>
+static int seg_loss_fwd_grad_impl(const char* fn, int dtype, int B, int h, int w, int ncls, const void* logits,
+                                  int H, int W, const long* label, int ignore, float* loss_out, float* grad_partials,
+                                  ClsOpts o, hipStream_t s) {
+  const int S = fused_scale(h, w, H, W);
+  DFM_CHECK_ARG(logits && label && loss_out && grad_partials && ncls <= MAXC && S,
+                "%s: bad argument (needs ncls <= 64 and H = S h, W = S w, S in {4, 8})", fn);
+  float* part = grad_partials;
+  float* lpart = part + (long)B * (h + 1) * (w + 1) * 4 * ncls;
+  DFM_DTYPE_SWITCH(dtype, T, return (launch_fused_tiles<T, OPT>(S, B, h, w, ncls, logits, H, W, label, ignore,
+                                                                loss_out, part, lpart, o, s)));
+}
+
+template <bool OPT>
+static int seg_loss_bwd_impl(const char* fn, int dtype, int B, int h, int w, int ncls, const void* logits, int H,
+                             int W, const long* label, int ignore, const float* loss_out, const float* gscale,
+                             float* dlogits, void* workspace, ClsOpts o, hipStream_t s) {
+  DFM_CHECK_ARG(logits && label && loss_out && dlogits && ncls <= MAXC && h <= H && w <= W,
+                "%s: bad argument (needs ncls <= 64 and an upsampling resize)", fn);
+  const long nl = (long)B * h * w * ncls;
+  if (workspace && tile_scale(h, w, H, W)) {
+    const int S = tile_scale(h, w, H, W);
+    DFM_DTYPE_SWITCH(dtype, T, return (launch_bwd_tiles<T, OPT>(S, B, h, w, ncls, logits, H, W, label, ignore,
+                                                                loss_out, gscale, (float*)workspace, dlogits, o, s)));
+  }
+  // other scales: separable x-pass into the workspace, then the y-pass
+  DFM_CHECK_ARG(workspace, "%s: needs dfm_seg_loss_bwd_workspace bytes of workspace", fn);
+  int RY, PJ;
+  DFM_CHECK_ARG(xpass_shape(w, W, RY, PJ), "%s: upsampling ratio W / w above ~120", fn);
+  float* rx = (float*)workspace;
+  const unsigned nblk = (unsigned)((long)B * ((H + RY - 1) / RY) * ((w + PJ - 1) / PJ));
+  const size_t lds = (size_t)XP_NT * (ncls + 1) * sizeof(float);
+  DFM_DTYPE_SWITCH(dtype, T, {
+    const auto kern = ncls <= 40 ? seg_loss_bwd_xpass_kernel<T, 40, OPT> : seg_loss_bwd_xpass_kernel<T, MAXC, OPT>;
+    if (lds > 64 * 1024) {
+      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      (void)hipGetLastError();  // a refused attribute must not read as this launch's error
+    }
+    DFM_LAUNCH(kern, dim3(nblk), dim3(XP_NT), lds, s, B, h, w, ncls, (const T*)logits, H, W, label, ignore, loss_out,
+               gscale, rx, RY, PJ, o);
+  });
+  DFM_LAUNCH_CHECK();
+  DFM_LAUNCH(seg_loss_bwd_ypass_kernel, dim3((unsigned)std::min(8192L, (nl + 255) / 256)), dim3(256), 0, s, B, h,
+             w, ncls, H, (const float*)rx, dlogits);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+extern "C" int dfm_seg_loss_fwd(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
+                                const long* label, int ignore, float* lse, float* loss_out, void* workspace,
+                                dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  return seg_loss_fwd_impl<false>(__func__, dtype, B, h, w, ncls, logits, H, W, label, ignore, lse, loss_out,
+                                  workspace, ClsOpts{nullptr, 0.f}, (hipStream_t)stream);
 }
 
 extern "C" size_t dfm_seg_loss_grad_partials_size(int B, int h, int w, int ncls, int H, int W) {
@@ -636,14 +780,8 @@ extern "C" int dfm_seg_loss_fwd_grad(int dtype, int B, int h, int w, int ncls, c
                                      const long* label, int ignore, float* loss_out, float* grad_partials,
                                      dfm_stream_t stream) {
   DFM_CHECK_DTYPE(dtype);
-  const int S = fused_scale(h, w, H, W);
-  DFM_CHECK_ARG(logits && label && loss_out && grad_partials && ncls <= MAXC && S,
-                "dfm_seg_loss_fwd_grad: bad argument (needs ncls <= 64 and H = S h, W = S w, S in {4, 8})");
-  hipStream_t s = (hipStream_t)stream;
-  float* part = grad_partials;
-  float* lpart = part + (long)B * (h + 1) * (w + 1) * 4 * ncls;
-  DFM_DTYPE_SWITCH(dtype, T, return launch_fused_tiles<T>(S, B, h, w, ncls, logits, H, W, label, ignore, loss_out, part,
-                                                          lpart, s));
+  return seg_loss_fwd_grad_impl<false>(__func__, dtype, B, h, w, ncls, logits, H, W, label, ignore, loss_out,
+                                       grad_partials, ClsOpts{nullptr, 0.f}, (hipStream_t)stream);
 }
 
 extern "C" int dfm_seg_loss_bwd_gather(int dtype_out, int B, int h, int w, int ncls, const float* grad_partials,
@@ -667,34 +805,187 @@ extern "C" int dfm_seg_loss_bwd(int dtype, int B, int h, int w, int ncls, const 
                                 const float* gscale, float* dlogits, void* workspace, dfm_stream_t stream) {
   (void)lse;
   DFM_CHECK_DTYPE(dtype);
-  DFM_CHECK_ARG(logits && label && loss_out && dlogits && ncls <= MAXC && h <= H && w <= W,
-                "dfm_seg_loss_bwd: bad argument (needs ncls <= 64 and an upsampling resize)");
-  hipStream_t s = (hipStream_t)stream;
-  const long nl = (long)B * h * w * ncls;
-  if (workspace && tile_scale(h, w, H, W)) {
-    const int S = tile_scale(h, w, H, W);
-    DFM_DTYPE_SWITCH(dtype, T, return launch_bwd_tiles<T>(S, B, h, w, ncls, logits, H, W, label, ignore, loss_out,
-                                                          gscale, (float*)workspace, dlogits, s));
-  }
-  // other scales: separable x-pass into the workspace, then the y-pass
-  DFM_CHECK_ARG(workspace, "dfm_seg_loss_bwd: needs dfm_seg_loss_bwd_workspace bytes of workspace");
-  int RY, PJ;
-  DFM_CHECK_ARG(xpass_shape(w, W, RY, PJ), "dfm_seg_loss_bwd: upsampling ratio W / w above ~120");
-  float* rx = (float*)workspace;
-  const unsigned nblk = (unsigned)((long)B * ((H + RY - 1) / RY) * ((w + PJ - 1) / PJ));
-  const size_t lds = (size_t)XP_NT * (ncls + 1) * sizeof(float);
-  DFM_DTYPE_SWITCH(dtype, T, {
-    const auto kern = ncls <= 40 ? seg_loss_bwd_xpass_kernel<T, 40> : seg_loss_bwd_xpass_kernel<T, MAXC>;
-    if (lds > 64 * 1024) {
-      (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipGetLastError();  // a refused attribute must not read as this launch's error
+  return seg_loss_bwd_impl<false>(__func__, dtype, B, h, w, ncls, logits, H, W, label, ignore, loss_out, gscale,
+                                  dlogits, workspace, ClsOpts{nullptr, 0.f}, (hipStream_t)stream);
+}
+
+// ---- class weights + label smoothing (builder.py:230 with the criterion's weight= / label_smoothing=):
+// the same four paths on the OPT = true kernels. weight: device float32 [ncls] or NULL (all 1).
+#define SEG_OPTS_CHECK(fn)                                                                                      \
+  DFM_CHECK_ARG(label_smoothing >= 0.f && label_smoothing < 1.f && ncls > 0, "%s: label_smoothing %g not in [0, 1)", \
+                fn, (double)label_smoothing)
+
+extern "C" int dfm_seg_loss_opts_fwd(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
+                                     const long* label, int ignore, const float* weight, float label_smoothing,
+                                     float* loss_out, void* workspace, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  SEG_OPTS_CHECK(__func__);
+  return seg_loss_fwd_impl<true>(__func__, dtype, B, h, w, ncls, logits, H, W, label, ignore, nullptr, loss_out,
+                                 workspace, ClsOpts{weight, label_smoothing}, (hipStream_t)stream);
+}
+
+extern "C" int dfm_seg_loss_opts_fwd_grad(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
+                                          const long* label, int ignore, const float* weight, float label_smoothing,
+                                          float* loss_out, float* grad_partials, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  SEG_OPTS_CHECK(__func__);
+  return seg_loss_fwd_grad_impl<true>(__func__, dtype, B, h, w, ncls, logits, H, W, label, ignore, loss_out,
+                                      grad_partials, ClsOpts{weight, label_smoothing}, (hipStream_t)stream);
+}
+
+extern "C" int dfm_seg_loss_opts_bwd(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
+                                     const long* label, int ignore, const float* weight, float label_smoothing,
+                                     const float* loss_out, const float* gscale, float* dlogits, void* workspace,
+                                     dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  SEG_OPTS_CHECK(__func__);
+  return seg_loss_bwd_impl<true>(__func__, dtype, B, h, w, ncls, logits, H, W, label, ignore, loss_out, gscale,
+                                 dlogits, workspace, ClsOpts{weight, label_smoothing}, (hipStream_t)stream);
+}
+#undef SEG_OPTS_CHECK
+
+// ---- online hard example mining (utils/loss_opr.py:137-187, ProbOhemCrossEntropy2d) as label
+// rewriting, which is what the reference does (target.masked_fill_): the mined-out pixels get the
+// ignore label and the loss kernels above run on the rewritten plane. Three kernels, no host sync:
+//   1. prob[p] = softmax(up(logits))[label[p]] per label pixel; 2.0 (out of range) where the label is invalid
+//   2. the k-th smallest valid prob, k = min_kept, by radix select: prob in [0, 1] orders like its bit
+//      pattern (< 2^30), so 3 passes of 10 bits: an integer histogram in LDS, integer atomics to global
+//      memory (deterministic), one block scanning the 1024 bins and narrowing the prefix
+//   3. label_out[p] = prob[p] <= threshold ? label[p] : ignore
+// threshold = max(thresh, k-th smallest) when 0 < min_kept <= num_valid; otherwise nothing is mined
+// (loss_opr.py:167,174) and threshold = 1 keeps every valid pixel.
+namespace {
+constexpr int RS_BITS = 10, RS_BINS = 1 << RS_BITS, RS_PASSES = 3;
+constexpr unsigned PROB_ONE = 0x3f800000u;  // bit pattern of 1.0f: valid probabilities are <= it
+constexpr int RS_STATE = 4;                  // state words after the histograms: prefix, remaining k, mining
+
+template <typename T, int NC>
+__global__ __launch_bounds__(256) void seg_ohem_prob_kernel(int B, int h, int w, int ncls, const T* __restrict__ lg,
+                                                            int H, int W, const long* __restrict__ label, int ignore,
+                                                            float* __restrict__ prob, unsigned* __restrict__ hist) {
+  const long n = (long)B * H * W;
+  const bool vec = ncls % 8 == 0 && ((uintptr_t)lg & 15) == 0;
+  if (blockIdx.x == 0)  // the select's histograms and state start at 0 (its kernels follow in stream order)
+    for (int i = threadIdx.x; i < RS_PASSES * RS_BINS + RS_STATE; i += blockDim.x) hist[i] = 0u;
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < n; p += (long)gridDim.x * blockDim.x) {
+    const int x = p % W, y = (p / W) % H, b = p / ((long)W * H);
+    const long lab = label[p];
+    float pr = 2.f;
+    if (lab != ignore && lab >= 0 && lab < ncls) {
+      float z[NC];
+      interp(lg, b, h, w, ncls, y, x, H, W, z, vec);
+      float m = -INFINITY, zl = 0.f;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        m = fmaxf(m, z[c]);
+        zl = (c == lab) ? z[c] : zl;
+      }
+      float se = 0.f;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) se += c < ncls ? __expf(z[c] - m) : 0.f;
+      pr = fminf(__expf(zl - m) / se, 1.f);
     }
-    DFM_LAUNCH(kern, dim3(nblk), dim3(XP_NT), lds, s, B, h, w, ncls, (const T*)logits, H, W, label, ignore, loss_out,
-               gscale, rx, RY, PJ);
-  });
+    prob[p] = pr;
+  }
+}
+
+// pass r histograms digit r (most significant first) of the valid probabilities whose higher digits
+// equal the prefix chosen so far
+__global__ __launch_bounds__(256) void seg_ohem_hist_kernel(long n, const float* __restrict__ prob, int pass,
+                                                            unsigned* hist) {
+  __shared__ unsigned lh[RS_BINS];
+  for (int i = threadIdx.x; i < RS_BINS; i += blockDim.x) lh[i] = 0u;
+  __syncthreads();
+  const int shift = RS_BITS * (RS_PASSES - 1 - pass);
+  const unsigned prefix = hist[RS_PASSES * RS_BINS];
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < n; p += (long)gridDim.x * blockDim.x) {
+    const unsigned key = __float_as_uint(prob[p]);
+    if (key <= PROB_ONE && (pass == 0 || (key >> (shift + RS_BITS)) == (prefix >> (shift + RS_BITS))))
+      atomicAdd(&lh[(key >> shift) & (RS_BINS - 1)], 1u);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < RS_BINS; i += blockDim.x)
+    if (lh[i]) atomicAdd(&hist[pass * RS_BINS + i], lh[i]);
+}
+
+// one block, one thread per bin: the bin holding the k-th smallest key extends the prefix. Pass 0 also
+// decides whether anything is mined and writes num_valid; the last pass writes the threshold.
+__global__ __launch_bounds__(RS_BINS) void seg_ohem_scan_kernel(int pass, unsigned* hist, float thresh,
+                                                                long min_kept, float* __restrict__ stats) {
+  __shared__ unsigned sc[2][RS_BINS];
+  unsigned* state = hist + RS_PASSES * RS_BINS;
+  const int t = threadIdx.x;
+  const unsigned v = hist[pass * RS_BINS + t];
+  const unsigned prefix = state[0];
+  unsigned k = state[1], mine = state[2];
+  int cur = 0;
+  sc[0][t] = v;
+  __syncthreads();
+  for (int o = 1; o < RS_BINS; o <<= 1) {  // inclusive scan of the bins
+    sc[cur ^ 1][t] = sc[cur][t] + (t >= o ? sc[cur][t - o] : 0u);
+    cur ^= 1;
+    __syncthreads();
+  }
+  const unsigned incl = sc[cur][t], total = sc[cur][RS_BINS - 1];
+  if (pass == 0) {  // total = the valid pixels
+    mine = min_kept > 0 && min_kept <= (long)total;
+    k = mine ? (unsigned)min_kept : 1u;
+    if (t == 0) {
+      state[2] = mine;
+      stats[0] = 1.f;
+      stats[1] = (float)total;
+    }
+  }
+  if (v != 0u && incl >= k && incl - v < k) {  // at most one bin; none when there is no valid pixel
+    const unsigned np = prefix | ((unsigned)t << (RS_BITS * (RS_PASSES - 1 - pass)));
+    state[0] = np;
+    state[1] = k - (incl - v);
+    if (pass == RS_PASSES - 1 && mine) stats[0] = fmaxf(thresh, __uint_as_float(np));
+  }
+}
+
+__global__ __launch_bounds__(256) void seg_ohem_relabel_kernel(long n, const float* __restrict__ prob,
+                                                               const long* __restrict__ label, int ignore,
+                                                               const float* __restrict__ stats,
+                                                               long* __restrict__ label_out) {
+  const float thr = stats[0];
+  for (long p = blockIdx.x * (long)blockDim.x + threadIdx.x; p < n; p += (long)gridDim.x * blockDim.x)
+    label_out[p] = prob[p] <= thr ? label[p] : (long)ignore;
+}
+}  // namespace
+
+extern "C" size_t dfm_seg_loss_ohem_workspace(int B, int H, int W) {
+  (void)B; (void)H; (void)W;
+  return (size_t)(RS_PASSES * RS_BINS + RS_STATE) * sizeof(unsigned);
+}
+
+extern "C" int dfm_seg_loss_ohem_relabel(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
+                                         const long* label, int ignore, float thresh, long min_kept, float* prob,
+                                         long* label_out, float* stats, void* workspace, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  DFM_CHECK_ARG(logits && label && prob && label_out && stats && workspace && ncls > 0 && ncls <= MAXC && B > 0 &&
+                    h > 0 && w > 0 && H > 0 && W > 0,
+                "dfm_seg_loss_ohem_relabel: bad argument (needs ncls <= 64)");
+  DFM_CHECK_ARG(thresh >= 0.f && thresh <= 1.f && min_kept >= 0,
+                "dfm_seg_loss_ohem_relabel: thresh %g not in [0, 1] or min_kept %ld negative", (double)thresh, min_kept);
+  const long n = (long)B * H * W;
+  DFM_CHECK_ARG(n < (1L << 31), "dfm_seg_loss_ohem_relabel: %ld label pixels (the counters are 32-bit)", n);
+  hipStream_t s = (hipStream_t)stream;
+  unsigned* hist = (unsigned*)workspace;
+  const dim3 g((unsigned)std::min((long)LOSS_BLOCKS, (n + 255) / 256));
+  DFM_DTYPE_SWITCH(dtype, T,
+                   DFM_LAUNCH((ncls <= 40 ? seg_ohem_prob_kernel<T, 40> : seg_ohem_prob_kernel<T, MAXC>), g, dim3(256),
+                              0, s, B, h, w, ncls, (const T*)logits, H, W, label, ignore, prob, hist));
   DFM_LAUNCH_CHECK();
-  DFM_LAUNCH(seg_loss_bwd_ypass_kernel, dim3((unsigned)std::min(8192L, (nl + 255) / 256)), dim3(256), 0, s, B, h,
-             w, ncls, H, (const float*)rx, dlogits);
+  for (int pass = 0; pass < RS_PASSES; ++pass) {
+    DFM_LAUNCH(seg_ohem_hist_kernel, g, dim3(256), 0, s, n, (const float*)prob, pass, hist);
+    DFM_LAUNCH_CHECK();
+    DFM_LAUNCH(seg_ohem_scan_kernel, dim3(1), dim3(RS_BINS), 0, s, pass, hist, thresh, min_kept, stats);
+    DFM_LAUNCH_CHECK();
+  }
+  DFM_LAUNCH(seg_ohem_relabel_kernel, g, dim3(256), 0, s, n, (const float*)prob, label, ignore, (const float*)stats,
+             label_out);
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
+

@@ -921,38 +921,59 @@ class UPerHead(nn.Module):
 
 # ========================================================================================== loss
 class SegLossFn(torch.autograd.Function):
-    """CE(bilinear_up(logits), label, ignore_index)[valid].mean() (builder.py:203,230), fused."""
+    """CE(bilinear_up(logits), label, ignore_index)[valid].mean() (builder.py:203,230), fused.
+    Optional trailing arguments (weight, label_smoothing, ohem_thresh, ohem_min_kept), the options of
+    losses.FusedSegLoss: class weights (float32 [ncls] on the device, or None) and label smoothing run on the
+    weighted kernel variants; mining (ohem_thresh not None) first rewrites the labels on the device
+    (loss_opr.py:157-185, no host sync, no gradient), and the loss runs on the rewritten plane. The mean is
+    over the kept-pixel count. Without them the plain kernels run, as they always did."""
 
     @staticmethod
-    def forward(ctx, logits_rows, B, h, w, label, ignore):
+    def forward(ctx, logits_rows, B, h, w, label, ignore, *opts):
         ncls = logits_rows.shape[1]
         label = label.contiguous()
         H, W = label.shape[-2:]
-        ctx.meta = (B, h, w, ncls, ignore)
+        weight, eps, ohem_thresh, ohem_min_kept = opts if opts else (None, 0.0, None, 0)
+        ctx.nin = 6 + len(opts)
+        if ohem_thresh is not None:
+            label = K.seg_loss_ohem_relabel(logits_rows, B, h, w, ncls, label, ohem_thresh, ohem_min_kept, ignore)[0]
+        ctx.opts = weighted = weight is not None or eps != 0.0
+        ctx.meta = (B, h, w, ncls, ignore, eps)
         if ctx.needs_input_grad[0] and K.seg_loss_grad_partials_size(B, h, w, ncls, H, W):
             # training at an integer factor (4, 8): the gradient's partials come out of the same pass
-            out, part = K.seg_loss_fwd_grad(logits_rows, B, h, w, ncls, label, ignore)
+            if weighted:
+                out, part = K.seg_loss_opts_fwd_grad(logits_rows, B, h, w, ncls, label, weight, eps, ignore)
+            else:
+                out, part = K.seg_loss_fwd_grad(logits_rows, B, h, w, ncls, label, ignore)
             ctx.save_for_backward(part, out)
             ctx.fused, ctx.dtype = True, logits_rows.dtype
         else:
-            out = K.seg_loss_fwd(logits_rows, B, h, w, ncls, label, ignore)
-            ctx.save_for_backward(logits_rows, label, out)
+            if weighted:
+                out = K.seg_loss_opts_fwd(logits_rows, B, h, w, ncls, label, weight, eps, ignore)
+            else:
+                out = K.seg_loss_fwd(logits_rows, B, h, w, ncls, label, ignore)
+            ctx.save_for_backward(logits_rows, label, out, *([weight] if weight is not None else []))
             ctx.fused = False
         return out[0] / out[1].clamp_min(1.0)
 
     @staticmethod
     def backward(ctx, g):
         K.TAG = "loss.bwd"
-        B, h, w, ncls, ignore = ctx.meta
+        B, h, w, ncls, ignore, eps = ctx.meta
+        none = (None,) * (ctx.nin - 1)
         gs = g.reshape(1).float().contiguous()
         if ctx.fused:
             part, out = ctx.saved_tensors
-            return K.seg_loss_bwd_gather(part, B, h, w, ncls, out, gs, ctx.dtype), None, None, None, None, None
-        logits_rows, label, out = ctx.saved_tensors
-        dl = K.seg_loss_bwd(logits_rows, B, h, w, ncls, label, out, gscale=gs, ignore=ignore)
+            return (K.seg_loss_bwd_gather(part, B, h, w, ncls, out, gs, ctx.dtype),) + none
+        logits_rows, label, out = ctx.saved_tensors[:3]
+        if ctx.opts:
+            weight = ctx.saved_tensors[3] if len(ctx.saved_tensors) > 3 else None
+            dl = K.seg_loss_opts_bwd(logits_rows, B, h, w, ncls, label, out, weight, eps, gscale=gs, ignore=ignore)
+        else:
+            dl = K.seg_loss_bwd(logits_rows, B, h, w, ncls, label, out, gscale=gs, ignore=ignore)
         if logits_rows.dtype != torch.float32:
             dl = K.cast(dl, logits_rows.dtype)
-        return dl, None, None, None, None, None
+        return (dl,) + none
 
 
 # ============================================================================ few-shot episodes

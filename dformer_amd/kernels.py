@@ -1344,6 +1344,81 @@ def seg_loss_bwd_gather(part, B, h, w, ncls, loss_out, gscale, dtype):
     return dl
 
 
+def _seg_loss_args(what, logits, B, h, w, ncls, label, weight):
+    """The buffer checks the criterion-option wrappers share; returns the label size (H, W)."""
+    if logits.dim() != 2 or not logits.is_contiguous() or tuple(logits.shape) != (B * h * w, ncls):
+        raise ValueError(f"{what}: logits {tuple(logits.shape)} are not contiguous [{B}*{h}*{w}, {ncls}]")
+    if label.dtype != torch.int64 or not label.is_contiguous() or label.dim() != 3 or label.shape[0] != B:
+        raise ValueError(f"{what}: label {tuple(label.shape)} {label.dtype} is not contiguous int64 [{B}, H, W]")
+    if weight is not None and (weight.dtype != torch.float32 or not weight.is_contiguous() or
+                               weight.numel() != ncls or weight.device != logits.device):
+        raise ValueError(f"{what}: weight {tuple(weight.shape)} {weight.dtype} on {weight.device} is not contiguous "
+                         f"float32 [{ncls}] on {logits.device}")
+    return tuple(label.shape[-2:])
+
+
+def seg_loss_opts_fwd(logits, B, h, w, ncls, label, weight=None, label_smoothing=0.0, ignore=255):
+    """seg_loss_fwd with class weights (float32 [ncls] or None) and label smoothing -> (sum, valid count)."""
+    H, W = _seg_loss_args("seg_loss_opts_fwd", logits, B, h, w, ncls, label, weight)
+    out = torch.empty(2, device=logits.device, dtype=torch.float32)
+    ws = _ws(lib.dfm_seg_loss_workspace(B, H, W), logits.device)
+    check(lib.dfm_seg_loss_opts_fwd(dtype_code(logits), B, h, w, ncls, ptr(logits), H, W, ptr(label), ignore,
+                                    ptr(weight), label_smoothing, ptr(out), ptr(ws), stream()),
+          "dfm_seg_loss_opts_fwd")
+    if ACCOUNT is not None:
+        _acct(0, logits.numel() * _es(logits) + label.numel() * 8)
+    return out
+
+
+def seg_loss_opts_bwd(logits, B, h, w, ncls, label, loss_out, weight=None, label_smoothing=0.0, gscale=None,
+                      ignore=255):
+    H, W = _seg_loss_args("seg_loss_opts_bwd", logits, B, h, w, ncls, label, weight)
+    if loss_out.dtype != torch.float32 or loss_out.numel() != 2:
+        raise ValueError(f"seg_loss_opts_bwd: loss_out {tuple(loss_out.shape)} {loss_out.dtype} is not float32 [2]")
+    dl = torch.empty(B * h * w, ncls, device=logits.device, dtype=torch.float32)
+    ws = _ws(lib.dfm_seg_loss_bwd_workspace(B, h, w, ncls, H, W), logits.device)
+    check(lib.dfm_seg_loss_opts_bwd(dtype_code(logits), B, h, w, ncls, ptr(logits), H, W, ptr(label), ignore,
+                                    ptr(weight), label_smoothing, ptr(loss_out), ptr(gscale), ptr(dl), ptr(ws),
+                                    stream()), "dfm_seg_loss_opts_bwd")
+    if ACCOUNT is not None:
+        _acct(0, logits.numel() * (_es(logits) + 4) + label.numel() * 8)
+    return dl
+
+
+def seg_loss_opts_fwd_grad(logits, B, h, w, ncls, label, weight=None, label_smoothing=0.0, ignore=255):
+    """seg_loss_fwd_grad with class weights and label smoothing -> (loss_out, partials for seg_loss_bwd_gather)."""
+    H, W = _seg_loss_args("seg_loss_opts_fwd_grad", logits, B, h, w, ncls, label, weight)
+    nb = seg_loss_grad_partials_size(B, h, w, ncls, H, W)
+    if nb == 0:
+        raise ValueError(f"seg_loss_opts_fwd_grad: ({h}, {w}) -> ({H}, {W}) is not an upsampling by 4 or 8")
+    out = torch.empty(2, device=logits.device, dtype=torch.float32)
+    part = torch.empty(nb // 4, device=logits.device, dtype=torch.float32)
+    check(lib.dfm_seg_loss_opts_fwd_grad(dtype_code(logits), B, h, w, ncls, ptr(logits), H, W, ptr(label), ignore,
+                                         ptr(weight), label_smoothing, ptr(out), ptr(part), stream()),
+          "dfm_seg_loss_opts_fwd_grad")
+    if ACCOUNT is not None:
+        _acct(0, logits.numel() * _es(logits) + label.numel() * 8)
+    return out, part
+
+
+def seg_loss_ohem_relabel(logits, B, h, w, ncls, label, thresh, min_kept, ignore=255):
+    """Online hard example mining as label rewriting (loss_opr.py:157-185), all on the device:
+    -> (label_out int64 like label, prob float32 like label, stats float32 [2] = (threshold, num_valid))."""
+    H, W = _seg_loss_args("seg_loss_ohem_relabel", logits, B, h, w, ncls, label, None)
+    if not 0.0 <= thresh <= 1.0 or min_kept < 0:
+        raise ValueError(f"seg_loss_ohem_relabel: thresh {thresh} not in [0, 1] or min_kept {min_kept} negative")
+    prob = torch.empty(B, H, W, device=logits.device, dtype=torch.float32)
+    out = torch.empty_like(label)
+    stats = torch.empty(2, device=logits.device, dtype=torch.float32)
+    ws = _ws(lib.dfm_seg_loss_ohem_workspace(B, H, W), logits.device)
+    check(lib.dfm_seg_loss_ohem_relabel(dtype_code(logits), B, h, w, ncls, ptr(logits), H, W, ptr(label), ignore,
+                                        float(thresh), int(min_kept), ptr(prob), ptr(out), ptr(stats), ptr(ws),
+                                        stream()), "dfm_seg_loss_ohem_relabel")
+    if ACCOUNT is not None:  # the prob plane is written once and read by 3 select passes and the relabel
+        _acct(0, logits.numel() * _es(logits) + label.numel() * (8 + 4 + 4 * 4 + 8))
+    return out, prob, stats
+
+
 # ------------------------------------------------------------- few-shot episodes (meta_forward)
 def fss_mask_footprint(mask, low_hw):
     """int64 masks [n, H, W] -> (foot [n, 2, h', w'], count [n, 2]) float32: the adjoint of the bilinear

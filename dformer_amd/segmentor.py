@@ -7,6 +7,8 @@ tuple through and crashes, SURVEY.md §3.0 #2 — the intended upstream semantic
 materialised when `return_logits` is True (the loss itself is fused and never needs it).
 With `decoder == "ham"` and a non-zero `cfg.aux_rate` an auxiliary FCNHead reads the stage-2 map and the
 training loss is CE(main) + aux_rate * CE(aux) (builder.py:138-143, 204-207, 231-232); no eval path runs it.
+`criterion` is the reference's plain CrossEntropyLoss or a losses.FusedSegLoss (class weights, label
+smoothing, hard example mining; applied to the main and the aux loss, all on the fused kernels).
 `decoder == "UPernet"` builds UPerHead on all four maps (logits at 1/4 resolution) and always the aux head
 with aux_rate 0.4 (builder.py:145-152).
 """
@@ -18,6 +20,7 @@ from .decoders import (DecoderHead, FCNHead, FssLossFn, FssProtoSimFn, LightHamH
                        _nhwc_rows)
 from .encoder import DFormer_Base, DFormer_Large, DFormer_Small, DFormer_Tiny, get_DFormerTrav
 from .functional import invalidate_weights
+from .losses import FusedSegLoss
 
 BACKBONES = {"DFormer-Tiny": (DFormer_Tiny, [32, 64, 128, 256]), "DFormer-Small": (DFormer_Small, [64, 128, 256, 512]),
              "DFormer-Base": (DFormer_Base, [64, 128, 256, 512]), "DFormer-Large": (DFormer_Large, [96, 192, 288, 576]),
@@ -28,8 +31,14 @@ BACKBONES = {"DFormer-Tiny": (DFormer_Tiny, [32, 64, 128, 256]), "DFormer-Small"
 def _check_criterion(criterion, ignore_index):
     """The loss is the fused kernel of builder.py:203,230: unweighted CrossEntropyLoss(reduction='none',
     ignore_index=cfg.background) followed by the mean over valid pixels (what train.py:189-194
-    passes). Anything else would be silently ignored, so it is rejected."""
+    passes), or a losses.FusedSegLoss with the same ignore_index (class weights, label smoothing, hard
+    example mining on the fused kernels). Anything else would be silently ignored, so it is rejected."""
     if criterion is None:
+        return
+    if isinstance(criterion, FusedSegLoss):
+        if criterion.ignore_index != ignore_index:
+            raise ValueError(f"EncoderDecoder: FusedSegLoss(ignore_index={criterion.ignore_index}) does not match "
+                             f"cfg.background = {ignore_index}")
         return
     ok = (isinstance(criterion, nn.CrossEntropyLoss) and criterion.weight is None and
           criterion.reduction == "none" and criterion.ignore_index == ignore_index and
@@ -38,7 +47,8 @@ def _check_criterion(criterion, ignore_index):
         raise NotImplementedError(
             f"EncoderDecoder: the fused segmentation loss implements CrossEntropyLoss(reduction='none', "
             f"ignore_index={ignore_index}) without class weights or label smoothing (utils/train.py:189-194); "
-            f"got {criterion!r}")
+            f"for class weights, label smoothing or hard example mining pass a "
+            f"dformer_amd.losses.FusedSegLoss; got {criterion!r}")
 
 
 def _aux_rate(cfg):
@@ -90,6 +100,10 @@ class EncoderDecoder(nn.Module):
             self.aux_head = FCNHead(self.channels[2], cfg.num_classes, norm_layer=norm_layer, bn_eps=bn_eps,
                                     bn_momentum=bn_mom, syncbn=syncbn)
         _check_criterion(criterion, getattr(cfg, "background", 255))
+        if isinstance(criterion, FusedSegLoss):  # one weight per output channel of every head it is applied to
+            criterion.check_classes(cfg.num_classes, "the decode head")
+            if self.aux_head is not None:
+                criterion.check_classes(self.aux_head.num_classes, "the aux head")
         self.criterion = criterion
         self.ignore_index = getattr(cfg, "background", 255)
         self.return_logits = True
@@ -150,11 +164,14 @@ class EncoderDecoder(nn.Module):
             low = self._low_logits(rgb, modal_x)
         rows, (B, h, w) = _nhwc_rows(low)
         K.TAG = "loss"
-        loss = SegLossFn.apply(rows.contiguous(), B, h, w, label.long(), self.ignore_index)
+        # a FusedSegLoss criterion's options apply to both heads (builder.py:230-232 calls the one criterion
+        # on each); the aux head is mined on its own probabilities
+        opts = self.criterion.kernel_options(rows.device) if isinstance(self.criterion, FusedSegLoss) else ()
+        loss = SegLossFn.apply(rows.contiguous(), B, h, w, label.long(), self.ignore_index, *opts)
         if aux is not None:  # builder.py:231-232: + aux_rate * CE(up(aux)) over the same valid pixels
             arows, (B, ah, aw) = _nhwc_rows(aux)
             loss = loss + self.aux_rate * SegLossFn.apply(arows.contiguous(), B, ah, aw, label.long(),
-                                                          self.ignore_index)
+                                                          self.ignore_index, *opts)
         out = self._upsample(low.detach(), rgb.shape[-2:]) if self.return_logits else low
         return loss, out
 

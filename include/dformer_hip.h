@@ -635,6 +635,39 @@ int dfm_seg_loss_fwd_grad(int dtype, int B, int h, int w, int ncls, const void* 
 int dfm_seg_loss_bwd_gather(int dtype_out, int B, int h, int w, int ncls, const float* grad_partials,
                             const float* loss_out, const float* gscale, void* dlogits, dfm_stream_t stream);
 
+/* Criterion options (builder.py:230 with the nn.CrossEntropyLoss arguments weight= / label_smoothing=): the
+ * loss paths above with, per valid pixel,
+ *   l = (1 - eps) w[y] (-log p_y) + eps / ncls sum_c w[c] (-log p_c)
+ * weight: device float32 [ncls] or NULL (all 1); label_smoothing eps in [0, 1). loss_out = (sum of l, valid
+ * COUNT): the mean divides by the pixel count, not the weight sum, as builder.py:230's reduction='none'
+ * followed by [label != background].mean() does. Workspaces and partials as for the plain entry points
+ * (dfm_seg_loss_workspace, dfm_seg_loss_bwd_workspace, dfm_seg_loss_grad_partials_size); the partials of
+ * dfm_seg_loss_opts_fwd_grad go to dfm_seg_loss_bwd_gather. Fixed summation orders, no float atomics.
+ * New symbols only: dfm_abi_version() stays 13. */
+int dfm_seg_loss_opts_fwd(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
+                          const long* label, int ignore, const float* weight, float label_smoothing,
+                          float* loss_out, void* workspace, dfm_stream_t stream);
+int dfm_seg_loss_opts_fwd_grad(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
+                               const long* label, int ignore, const float* weight, float label_smoothing,
+                               float* loss_out, float* grad_partials, dfm_stream_t stream);
+int dfm_seg_loss_opts_bwd(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
+                          const long* label, int ignore, const float* weight, float label_smoothing,
+                          const float* loss_out, const float* gscale, float* dlogits, void* workspace,
+                          dfm_stream_t stream);
+
+/* Online hard example mining (utils/loss_opr.py:137-187, ProbOhemCrossEntropy2d.forward) as label rewriting:
+ * prob [B][H][W] float32 = the softmax probability of the true class of the upsampled logits (2.0 where the
+ * label is invalid); stats float32 [2] = (threshold, num_valid); label_out [B][H][W] int64 = label where
+ * prob <= threshold, `ignore` elsewhere. With 0 < min_kept <= num_valid, threshold = max(thresh, the
+ * min_kept-th smallest valid prob) (loss_opr.py:173-179, ties kept); otherwise nothing is mined
+ * (loss_opr.py:167,174) and threshold = 1. The k-th smallest is a radix select over integer histograms on the
+ * device: no host synchronisation, deterministic. Any loss entry point then runs on label_out. workspace:
+ * dfm_seg_loss_ohem_workspace bytes; thresh in [0, 1]; B * H * W < 2^31. */
+size_t dfm_seg_loss_ohem_workspace(int B, int H, int W);
+int dfm_seg_loss_ohem_relabel(int dtype, int B, int h, int w, int ncls, const void* logits, int H, int W,
+                              const long* label, int ignore, float thresh, long min_kept, float* prob,
+                              long* label_out, float* stats, void* workspace, dfm_stream_t stream);
+
 /* ---------------------------------------------------------------- few-shot episodes (meta_forward)
  * models/builder.py:237-320 collapsed onto stage-3 sized tensors: bilinear upsampling is
  * linear, so nothing of size C x H x W is formed. Two classes throughout, [bg, fg] (builder.py:296); 255 is
