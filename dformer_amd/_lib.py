@@ -218,6 +218,13 @@ _SIGS = {
     "dfm_adamw_dev": (c_int, [c_long, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, P, c_int, P]),
     "dfm_adamw_amp": (c_int, [c_long, P, P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, P, c_int, P]),
     "dfm_loss_scale_update": (c_int, [P, P, c_float, c_float, c_int, P]),
+    "dfm_grad_accumulate": (c_int, [c_long, P, P, P]),
+    "dfm_grad_sumsq_blocks": (c_int, []),
+    "dfm_grad_sumsq": (c_int, [c_long, P, P, P, P, P]),
+    "dfm_grad_clip_coef": (c_int, [c_int, P, c_float, P, c_float, P, P, P]),
+    "dfm_adamw_opt": (c_int, [c_long, P, P, c_int, P, P, P, P, P, P, P, P, c_float, c_float, c_float, c_float,
+                              c_float, c_float, P, c_int, P]),
+    "dfm_loss_scale_update_win": (c_int, [P, P, c_float, c_float, c_int, P, P]),
     "dfm_trace_set": (c_int, [c_int, ctypes.c_char_p]),
     "dfm_trace_take": (c_int, [ctypes.POINTER(c_void_p), c_int]),
     "dfm_trace_read": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_float), c_int]),

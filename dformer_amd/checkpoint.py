@@ -82,9 +82,20 @@ def load_model(model, src, optimizer=None):
     return model
 
 
+def _unwrap(sd):
+    return OrderedDict((k[7:] if k.split(".")[0] == "module" else k, v) for k, v in sd.items())
+
+
 def save_checkpoint(path, model, optimizer, epoch, iteration):
-    sd = OrderedDict((k[7:] if k.split(".")[0] == "module" else k, v) for k, v in model.state_dict().items())
-    torch.save({"model": sd, "optimizer": optimizer.state_dict(), "epoch": epoch, "iteration": iteration}, path)
+    """With FusedAdamW(ema_decay=...) the file also holds `state_dict_ema`, the model's state dict on
+    the averaged weights: the entry load_pretrained_backbone prefers (the averages are stored there
+    once, not again inside "optimizer")."""
+    osd = optimizer.state_dict()
+    raw = {"model": _unwrap(model.state_dict()), "optimizer": osd, "epoch": epoch, "iteration": iteration}
+    if "ema" in osd:
+        del osd["ema"]
+        raw["state_dict_ema"] = _unwrap(optimizer.ema_state_dict(model))
+    torch.save(raw, path)
 
 
 def restore_checkpoint(path, model, optimizer):
@@ -92,4 +103,6 @@ def restore_checkpoint(path, model, optimizer):
     raw = _read(path)
     load_model(model, raw["model"], optimizer)
     optimizer.load_state_dict(raw["optimizer"])
+    if "state_dict_ema" in raw and getattr(optimizer, "ema_decay", None) is not None:
+        optimizer.load_ema_state_dict(model, raw["state_dict_ema"])
     return raw["epoch"] + 1, raw["iteration"]

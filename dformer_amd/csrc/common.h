@@ -122,6 +122,24 @@ template <int G> DFM_INLINE float group_sum(float v) {
   return v;
 }
 
+// GradScaler.update (torch/amp/grad_scaler.py _amp_update_scale_) on the loss scaler's device state
+// amp = {scale, growth_tracker, applied_steps, skipped}; clears the overflow flag. One lane calls it.
+DFM_INLINE void loss_scale_step(float* amp, int* flag, float growth, float backoff, int interval) {
+  if (flag[0]) {
+    amp[0] *= backoff;
+    amp[1] = 0.f;
+    amp[3] += 1.f;
+  } else {
+    amp[2] += 1.f;
+    amp[1] += 1.f;
+    if (amp[1] >= (float)interval) {
+      amp[0] *= growth;
+      amp[1] = 0.f;
+    }
+  }
+  flag[0] = 0;
+}
+
 // 8 consecutive T elements <-> floats
 template <typename T> DFM_INLINE void ld8(const T* p, float* v);
 template <> DFM_INLINE void ld8<bf16_t>(const bf16_t* p, float* v) {

@@ -526,19 +526,7 @@ __global__ void adamw_dev_kernel(long n, float* __restrict__ p, const float* __r
 __global__ void loss_scale_update_kernel(float* __restrict__ amp, int* __restrict__ flag, float growth,
                                          float backoff, int interval) {
   if (threadIdx.x != 0) return;
-  if (flag[0]) {
-    amp[0] *= backoff;
-    amp[1] = 0.f;
-    amp[3] += 1.f;
-  } else {
-    amp[2] += 1.f;
-    amp[1] += 1.f;
-    if (amp[1] >= (float)interval) {
-      amp[0] *= growth;
-      amp[1] = 0.f;
-    }
-  }
-  flag[0] = 0;
+  loss_scale_step(amp, flag, growth, backoff, interval);
 }
 
 // o1 = src * m1, o2 = src * m2 (the two products of one gradient against the two factors of

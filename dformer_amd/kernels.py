@@ -1572,3 +1572,79 @@ def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0,
                             grad_scale, ptr(bf16_copy), cdt, stream()), "dfm_adamw")
     if ACCOUNT is not None:
         _acct(0, p.numel() * (28 + (2 if bf16_copy is not None else 0)))
+
+
+# ------------------------------------------------------------------------- optimizer options
+def _f32_flat(t, what):
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise TypeError(f"dformer_amd: {what} must be a contiguous float32 buffer")
+    return t
+
+
+def _win(win):
+    """The window state {micro_index, accum_steps}: int32 [2] on the device, or None."""
+    if win is not None and (win.dtype != torch.int32 or win.numel() < 2):
+        raise ValueError("dformer_amd: win is int32 [2]")
+    return ptr(win)
+
+
+def grad_accumulate(acc, g):
+    """acc += g over flat float32 buffers (p.grad += g of a backward without zero_grad())."""
+    if acc.numel() != g.numel():
+        raise ValueError(f"grad_accumulate: {acc.numel()} vs {g.numel()} elements")
+    check(lib.dfm_grad_accumulate(acc.numel(), ptr(_f32_flat(acc, "acc")), ptr(_f32_flat(g, "g")), stream()),
+          "dfm_grad_accumulate")
+    if ACCOUNT is not None:
+        _acct(0, acc.numel() * 12)
+
+
+def sumsq_blocks():
+    """Partials dfm_grad_sumsq writes per buffer."""
+    return lib.dfm_grad_sumsq_blocks()
+
+
+def grad_sumsq(g, part, flag=None, win=None):
+    """Stage one of the global gradient norm: sumsq_blocks() float32 partials of sum g^2 into `part`
+    (this buffer's slice of the partial buffer); with `flag` also grad_nonfinite over the same read."""
+    if part.numel() < sumsq_blocks():
+        raise ValueError(f"grad_sumsq: {part.numel()} partial slots, {sumsq_blocks()} needed")
+    check(lib.dfm_grad_sumsq(g.numel(), ptr(_f32_flat(g, "g")), ptr(_f32_flat(part, "part")), ptr(flag), _win(win),
+                             stream()), "dfm_grad_sumsq")
+    if ACCOUNT is not None:
+        _acct(0, g.numel() * 4)
+
+
+def grad_clip_coef(part, grad_scale, max_norm, clip_state, amp=None, win=None):
+    """Stage two over the partials of every buffer: clip_state (float32 [2]) = {total_norm, coef} of
+    torch.nn.utils.clip_grad_norm_(max_norm) for gradients g * grad_scale (/ the loss scale amp[0])."""
+    if clip_state.numel() < 2 or clip_state.dtype != torch.float32:
+        raise ValueError("grad_clip_coef: clip_state is float32 [2]")
+    check(lib.dfm_grad_clip_coef(part.numel(), ptr(_f32_flat(part, "part")), grad_scale, ptr(amp), max_norm,
+                                 ptr(clip_state), _win(win), stream()), "dfm_grad_clip_coef")
+    if ACCOUNT is not None:
+        _acct(0, part.numel() * 4)
+
+
+def adamw_opt(p, g, m, v, hyper, beta1, beta2, eps, weight_decay, grad_scale=1.0, bf16_copy=None, amp=None,
+              flag=None, clip_state=None, win=None, ema=None, ema_decay=0.0, clear_g=False):
+    """adamw(hyper=...) with the optimizer options, each off when None: the gradient times
+    clip_state[1]; no write unless `win` (int32 {micro_index, accum_steps}) is on its last
+    micro-step; `ema` updated in the same pass; clear_g zeroes g (the accumulation buffer)."""
+    n = p.numel()
+    for t, what in ((g, "g"), (m, "m"), (v, "v"), (ema, "ema"), (bf16_copy, "bf16_copy")):
+        if t is not None and t.numel() != n:
+            raise ValueError(f"adamw_opt: {what} has {t.numel()} elements, p has {n}")
+    cdt = dtype_code(bf16_copy) if bf16_copy is not None else 0
+    check(lib.dfm_adamw_opt(n, ptr(_f32_flat(p, "p")), ptr(_f32_flat(g, "g")), int(clear_g), ptr(_f32_flat(m, "m")),
+                            ptr(_f32_flat(v, "v")), ptr(hyper), ptr(amp), ptr(flag), ptr(clip_state), _win(win),
+                            ptr(None if ema is None else _f32_flat(ema, "ema")), ema_decay, beta1, beta2, eps,
+                            weight_decay, grad_scale, ptr(bf16_copy), cdt, stream()), "dfm_adamw_opt")
+    if ACCOUNT is not None:
+        _acct(0, n * (28 + (2 if bf16_copy is not None else 0) + (8 if ema is not None else 0)
+                      + (4 if clear_g else 0)))
+
+
+def loss_scale_update_win(amp, flag, growth, backoff, interval, win=None):
+    """loss_scale_update that leaves the scaler alone inside an accumulation window."""
+    check(lib.dfm_loss_scale_update_win(ptr(amp), ptr(flag), growth, backoff, interval, _win(win), stream()),
+          "dfm_loss_scale_update_win")

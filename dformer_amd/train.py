@@ -3,7 +3,8 @@
   group_weight      utils/init_func.py:26-70 (decay / no-decay groups; layer_scale_* and the custom
                     LayerNorm params fall in no group and are never updated — reproduced)
   FusedAdamW        torch.optim.AdamW(lr, betas=(0.9, 0.999), wd) of train.py:210-216 as one HIP launch
-                    per group over flat float32 buffers, also refreshing the bf16 GEMM weight copies
+                    per group over flat float32 buffers, also refreshing the bf16 GEMM weight copies;
+                    optionally gradient accumulation, clip_grad_norm_ and a weight EMA (csrc/optim.hip)
   WarmUpPolyLR      utils/lr_policy.py:22-36
   GradBuckets       DDP-style bucketed gradient all-reduce (SUM, /world folded into AdamW), launched
                     from post-accumulate-grad hooks so RCCL overlaps the rest of the backward pass
@@ -11,6 +12,8 @@
                     scaled backward, inf/nan check over the flat gradients on the device, skipped
                     step + backoff on overflow, growth every 2000 clean steps
 """
+import contextlib
+
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -132,6 +135,7 @@ class _FlatGroup:
         self.m = torch.zeros(n, device=device, dtype=torch.float32)
         self.v = torch.zeros(n, device=device, dtype=torch.float32)
         self.shadow = torch.empty(n, device=device, dtype=shadow_dtype) if shadow_dtype != torch.float32 else None
+        self.acc = self.ema = None  # FusedAdamW's accum_steps / ema_decay buffers
         self.slots = {}
         off = 0
         for p in self.params:
@@ -304,6 +308,11 @@ class LossScaler:
         K.loss_scale_update(self.state, self.found_inf, self.growth_factor, self.backoff_factor,
                             self.growth_interval)
 
+    def update_device_win(self, win):
+        """update_device once per accumulation window: nothing moves unless `win` is on its last micro-step."""
+        K.loss_scale_update_win(self.state, self.found_inf, self.growth_factor, self.backoff_factor,
+                                self.growth_interval, win)
+
     def update(self, found_inf):
         """GradScaler.update on the state from the host (what dfm_loss_scale_update does on the
         device; used where no device is involved)."""
@@ -327,10 +336,30 @@ class FusedAdamW:
     advance it for a parameter without a gradient, whereas here a parameter that was skipped in
     some steps (its value and moments restored, see GradBuckets.finish) still uses the global count
     in the bias correction. DFormer's unused parameters never get a gradient, so this only matters
-    for a model whose used set changes between steps."""
+    for a model whose used set changes between steps.
+
+    Options, each off by default (the step then launches what it always did, with no extra buffer):
+      accum_steps = k     every train_step call adds its gradient into a flat accumulator; the k-th
+                          call of a window updates from the accumulated mean and clears it. step_count,
+                          the bias correction and the loss scaler count windows; an fp16 overflow
+                          anywhere in the window skips the window's update.
+      max_grad_norm       torch.nn.utils.clip_grad_norm_ over the two groups' gradients, after the
+                          unscale on the fp16 path; grad_norm() reads the last window's norm.
+      ema_decay = d       ema = d * ema + (1 - d) * p after every applied update (ema_state_dict,
+                          ema_weights).
+    The window position, the clip coefficient and the overflow flag live on the device: every
+    train_step call issues the same launches and the kernels decide, so one captured graph serves
+    every micro-step (GraphedTrainStep)."""
 
     def __init__(self, model, lr=6e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, world=1,
-                 compute_dtype=torch.float32, bucket_bytes=25 << 20):
+                 compute_dtype=torch.float32, bucket_bytes=25 << 20, accum_steps=1, max_grad_norm=None,
+                 ema_decay=None):
+        if int(accum_steps) != accum_steps or accum_steps < 1:
+            raise ValueError(f"accum_steps must be an integer >= 1, got {accum_steps!r}")
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError(f"max_grad_norm must be > 0, got {max_grad_norm!r}")
+        if ema_decay is not None and not 0 <= ema_decay < 1:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
         decay, no_decay = group_weight(model)
         self.full_groups = (decay, no_decay)  # reference group lists, incl. frozen params (state_dict indices)
         dev = next(model.parameters()).device
@@ -347,6 +376,23 @@ class FusedAdamW:
         # refreshes it before every replay and sets external_hyper)
         self.hyper = torch.zeros(2, device=dev, dtype=torch.float32)
         self.external_hyper = False
+        self.accum_steps, self.max_grad_norm, self.ema_decay = int(accum_steps), max_grad_norm, ema_decay
+        self._micro = 0  # position of the next train_step call in its accumulation window
+        self.options = self.accum_steps > 1 or max_grad_norm is not None or ema_decay is not None
+        # {micro_index, accum_steps} on the device, refreshed like hyper
+        self.win = None
+        if self.accum_steps > 1:
+            self.win = torch.tensor([0, self.accum_steps], device=dev, dtype=torch.int32)
+        # {total_norm, coef} of the last window, written by the norm's second stage
+        self.clip_state = torch.zeros(2, device=dev, dtype=torch.float32) if max_grad_norm is not None else None
+        self.partials = None  # the norm's per-block partials, one slice per group
+        if self.options and (max_grad_norm is not None or self.scaler is not None):
+            self.partials = torch.zeros(len(self.groups) * K.sumsq_blocks(), device=dev, dtype=torch.float32)
+        for g in self.groups:
+            if self.accum_steps > 1:
+                g.acc = torch.zeros_like(g.grad)
+            if ema_decay is not None:
+                g.ema = g.flat.clone()
         self.buckets = GradBuckets(self.groups, world, bucket_bytes)
         grouped = {id(p) for g in self.groups for p in g.params}
         # layer_scale_* and the custom LayerNorm params: in no group (never updated, like the reference)
@@ -373,37 +419,130 @@ class FusedAdamW:
         self.buckets.finish()
         for p in self.ungrouped:
             p.grad = None
-        gscale = 1.0 / self.world
+        gscale = 1.0 / (self.world * self.accum_steps)
         sc = self.scaler
-        if sc is not None:  # GradScaler.unscale_ / step / update, decided on the device
+        if sc is not None and not self.options:  # GradScaler.unscale_ / step / update, decided on the device
             sc.flag_nonfinite([g.grad for g in self.groups])
-        else:
-            self._steps += 1
+        micro = self.advance()
         lr = self.lr if lr is None else lr
         if not self.external_hyper:
-            self.hyper[0].fill_(lr)
-            if sc is None:
-                self.hyper[1].fill_(float(self._steps))
+            self.refresh_device(lr, micro)
         # parameters that got no gradient this step: torch.optim.AdamW skips them (no decay, no
-        # momentum step), so their value / moments are put back after the flat update
-        keep = [(g, off, k, g.flat[off:off + k].clone(), g.m[off:off + k].clone(), g.v[off:off + k].clone())
+        # momentum step), so their value / moments are put back after the flat update (and their
+        # average, which an update with the decayed value would have moved)
+        keep = [(g, off, k, g.flat[off:off + k].clone(), g.m[off:off + k].clone(), g.v[off:off + k].clone(),
+                 g.ema[off:off + k].clone() if g.ema is not None else None)
                 for g, off, k in self.buckets.unfired]
-        for g in self.groups:
-            K.adamw(g.flat, g.grad, g.m, g.v, lr, self.betas[0], self.betas[1], self.eps, g.wd, 1, gscale, g.shadow,
-                    hyper=self.hyper, amp=sc.state if sc is not None else None,
-                    flag=sc.found_inf if sc is not None else None)
-        if sc is not None:
-            sc.update_device()
-        for g, off, k, p0, m0, v0 in keep:
+        if self.options:
+            self._update_with_options(gscale)
+        else:
+            for g in self.groups:
+                K.adamw(g.flat, g.grad, g.m, g.v, lr, self.betas[0], self.betas[1], self.eps, g.wd, 1, gscale,
+                        g.shadow, hyper=self.hyper, amp=sc.state if sc is not None else None,
+                        flag=sc.found_inf if sc is not None else None)
+            if sc is not None:
+                sc.update_device()
+        for g, off, k, p0, m0, v0, e0 in keep:
             g.flat[off:off + k].copy_(p0)
             g.m[off:off + k].copy_(m0)
             g.v[off:off + k].copy_(v0)
             if g.shadow is not None:
                 g.shadow[off:off + k].copy_(p0)
+            if e0 is not None:
+                g.ema[off:off + k].copy_(e0)
         invalidate_weights()
         for g in self.groups:
             g.register_shadows()
 
+    def advance(self):
+        """Host bookkeeping of one train_step call: returns the call's position in its accumulation
+        window and counts the window on its last micro-step (with the fp16 scaler the device counts)."""
+        micro = self._micro
+        self._micro = (micro + 1) % self.accum_steps
+        if self.scaler is None and micro == self.accum_steps - 1:
+            self._steps += 1
+        return micro
+
+    def refresh_device(self, lr, micro):
+        """The per-call host state of a step, written where the kernels read it (a captured graph's
+        owner does this before every replay): lr, the applied-step count, the window position."""
+        self.hyper[0].fill_(lr)
+        if self.scaler is None:
+            self.hyper[1].fill_(float(self._steps))
+        if self.win is not None:
+            self.win[0].fill_(micro)
+
+    def _update_with_options(self, gscale):
+        """accumulate -> (nonfinite, norm) -> update, the same launches on every micro-step: what is
+        not due before the window's last micro-step returns at once on the device (`win`)."""
+        sc = self.scaler
+        amp, flag = (sc.state, sc.found_inf) if sc is not None else (None, None)
+        accum = self.accum_steps > 1
+        if accum:
+            for g in self.groups:
+                K.grad_accumulate(g.acc, g.grad)
+        grads = [g.acc if accum else g.grad for g in self.groups]
+        if self.partials is not None:  # one read serves the norm and the scaler's inf / nan check
+            nb = K.sumsq_blocks()
+            for j, gr in enumerate(grads):
+                K.grad_sumsq(gr, self.partials[j * nb:(j + 1) * nb], flag=flag, win=self.win)
+            if self.max_grad_norm is not None:
+                K.grad_clip_coef(self.partials, gscale, self.max_grad_norm, self.clip_state, amp=amp, win=self.win)
+        for g, gr in zip(self.groups, grads):
+            K.adamw_opt(g.flat, gr, g.m, g.v, self.hyper, self.betas[0], self.betas[1], self.eps, g.wd, gscale,
+                        g.shadow, amp=amp, flag=flag, clip_state=self.clip_state, win=self.win, ema=g.ema,
+                        ema_decay=self.ema_decay or 0.0, clear_g=accum)
+        if sc is not None:
+            sc.update_device_win(self.win)
+
+    def grad_norm(self):
+        """The last applied window's global gradient norm before clipping (max_grad_norm only).
+        Reads the device: it synchronises, so it is for logging."""
+        if self.clip_state is None:
+            raise RuntimeError("grad_norm() needs FusedAdamW(max_grad_norm=...)")
+        return float(self.clip_state[0])
+
+    def _ema_slots(self, model):
+        """(state_dict key, group, offset, numel, parameter) of the model's parameters that have an average."""
+        if self.ema_decay is None:
+            raise RuntimeError("no weight average: build FusedAdamW with ema_decay=...")
+        for name, p in model.named_parameters():
+            for g in self.groups:
+                if p in g.slots:
+                    off, k = g.slots[p]
+                    yield name, g, off, k, p
+
+    def ema_state_dict(self, model):
+        """model.state_dict() with every grouped parameter replaced by its average; buffers (BatchNorm
+        statistics) and the parameters in no group are the live ones."""
+        sd = model.state_dict()
+        for name, g, off, k, p in self._ema_slots(model):
+            sd[name] = g.ema[off:off + k].view_as(p).clone()
+        return sd
+
+    def load_ema_state_dict(self, model, sd):
+        """The averages back from an ema_state_dict (a checkpoint's state_dict_ema)."""
+        for name, g, off, k, p in self._ema_slots(model):
+            g.ema[off:off + k].copy_(sd[name].reshape(-1))
+
+    def _swap_ema(self):
+        for g in self.groups:
+            live = g.flat.clone()
+            g.flat.copy_(g.ema)
+            g.ema.copy_(live)
+        self.refresh_shadows()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run evaluate / evaluate_msf / predict on the averaged weights: parameters and averages are
+        swapped in place (16-bit shadows refreshed, weight caches invalidated) and swapped back on exit."""
+        if self.ema_decay is None:
+            raise RuntimeError("no weight average: build FusedAdamW with ema_decay=...")
+        self._swap_ema()
+        try:
+            yield
+        finally:
+            self._swap_ema()
 
     def refresh_shadows(self):
         """After parameters were overwritten in place (load_state_dict): refresh the bf16 copies."""
@@ -422,34 +561,69 @@ class FusedAdamW:
                     if k != "params"}
         state, groups, idx = {}, [], 0
         steps = self.step_count  # one read (a device sync with the fp16 scaler), not one per parameter
+        ema, acc = {}, {}  # per parameter index like `state`
         for plist, g in zip(self.full_groups, self.groups):
             ids = []
             for p in plist:
-                if p in g.slots and steps > 0:
+                if p in g.slots:
                     off, k = g.slots[p]
-                    state[idx] = {"step": torch.tensor(float(steps)),
-                                  "exp_avg": g.m[off:off + k].view_as(p).detach().clone(),
-                                  "exp_avg_sq": g.v[off:off + k].view_as(p).detach().clone()}
+                    if steps > 0:
+                        state[idx] = {"step": torch.tensor(float(steps)),
+                                      "exp_avg": g.m[off:off + k].view_as(p).detach().clone(),
+                                      "exp_avg_sq": g.v[off:off + k].view_as(p).detach().clone()}
+                    if g.ema is not None:
+                        ema[idx] = g.ema[off:off + k].view_as(p).clone()
+                    if g.acc is not None and self._micro:  # mid-window: the gradients summed so far
+                        acc[idx] = g.acc[off:off + k].view_as(p).clone()
                 ids.append(idx)
                 idx += 1
             grp = dict(defaults)
             grp.update(lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=g.wd, params=ids)
             groups.append(grp)
-        return {"state": state, "param_groups": groups}
+        sd = {"state": state, "param_groups": groups}
+        # the options' state under keys of their own (torch.optim.AdamW.load_state_dict ignores them)
+        if self.ema_decay is not None:
+            sd["ema"] = ema
+        if self.accum_steps > 1:
+            sd["window"] = {"micro_index": self._micro, "accum_steps": self.accum_steps, "acc": acc}
+        return sd
 
     def load_state_dict(self, sd):
         groups = sd["param_groups"]
         if len(groups) != 2:
             raise ValueError(f"expected the two group_weight groups, got {len(groups)}")
         steps = set()
+        ema = sd.get("ema") if self.ema_decay is not None else None
+        win = sd.get("window") if self.accum_steps > 1 else None
+        if win is not None and win["accum_steps"] != self.accum_steps:
+            if win["micro_index"]:
+                raise ValueError(f"saved mid-window with accum_steps={win['accum_steps']}, "
+                                 f"this optimizer has {self.accum_steps}")
+            win = None
+        for g in self.groups:  # without a saved average / window: start from the parameters / a new window
+            if g.ema is not None and ema is None:
+                g.ema.copy_(g.flat)
+            if g.acc is not None:
+                g.acc.zero_()
+        self._micro = win["micro_index"] if win is not None else 0
+
+        def entry(d, idx):
+            return d.get(idx, d.get(str(idx)))
+
         for plist, g, grp in zip(self.full_groups, self.groups, groups):
             if len(grp["params"]) != len(plist):
                 raise ValueError(f"param group size mismatch: {len(grp['params'])} vs {len(plist)}")
             for p, idx in zip(plist, grp["params"]):
-                st = sd["state"].get(idx, sd["state"].get(str(idx)))
-                if st is None or p not in g.slots:
+                if p not in g.slots:
                     continue
                 off, k = g.slots[p]
+                if ema is not None and entry(ema, idx) is not None:
+                    g.ema[off:off + k].copy_(entry(ema, idx).reshape(-1))
+                if win is not None and entry(win["acc"], idx) is not None:
+                    g.acc[off:off + k].copy_(entry(win["acc"], idx).reshape(-1))
+                st = entry(sd["state"], idx)
+                if st is None:
+                    continue
                 g.m[off:off + k].copy_(st["exp_avg"].reshape(-1))
                 g.v[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
                 steps.add(int(float(st["step"])))
@@ -476,8 +650,10 @@ class GraphedTrainStep:
     the host (~23 us of Python / autograd per eager launch) no longer paces the device.
 
     rgb / depth / label are the static input buffers: copy each new batch into them in place. The
-    optimizer's lr and step count live in a device tensor refreshed before every replay (the only
-    per-step host state of the step); dropout / DropPath draws advance with torch's graph-safe
+    optimizer's lr, step count and accumulation-window position live in device tensors refreshed
+    before every replay (the only per-step host state of the step, FusedAdamW.refresh_device): with
+    accum_steps = k the one graph is replayed for every micro-step, and the kernels read whether an
+    update is due. Dropout / DropPath draws advance with torch's graph-safe
     Philox offsets. Needs every kernel of the step on torch's current stream or streams forked from
     it (true of this package) and no host synchronisation inside the step."""
 
@@ -497,27 +673,24 @@ class GraphedTrainStep:
             # once in capture_end): nothing of the eager steps may still be pending when capture begins
             dist.distributed_c10d._get_default_group()._wait_for_pending_works()
         self.graph = torch.cuda.CUDAGraph()
-        opt.external_hyper = True  # inside the graph AdamW only reads hyper
+        opt.external_hyper = True  # inside the graph AdamW only reads hyper (and the window state)
+        self._micro = opt._micro  # the captured call's place in its accumulation window
         try:
             # thread-local capture: the process group's watchdog thread keeps querying the events of
             # earlier (eager) collectives, which under the default global mode invalidates the capture
             with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self.loss = train_step(model, opt, rgb, depth, label)  # host step_count advanced once here
+                self.loss = train_step(model, opt, rgb, depth, label)  # host counters advanced once here
         finally:
             opt.external_hyper = False
 
-    def _set_hyper(self, lr, step):
-        self.opt.hyper[0].fill_(self.opt.lr if lr is None else lr)
-        if step is not None:
-            self.opt.hyper[1].fill_(float(step))
-
     def __call__(self, lr=None):
-        """One training step (the first call replays the captured step itself)."""
-        amp = self.opt.scaler is not None  # the fp16 step counts its applied steps on the device
-        if getattr(self, "_replayed", False) and not amp:
-            self.opt._steps += 1
+        """One training step (the first call replays the captured step itself). The graph is the
+        same for every micro-step of an accumulation window: only the device state refreshed here
+        (lr, step count, window position) tells the kernels which one this is."""
+        if getattr(self, "_replayed", False):
+            self._micro = self.opt.advance()
         self._replayed = True
-        self._set_hyper(lr, None if amp else self.opt._steps)
+        self.opt.refresh_device(self.opt.lr if lr is None else lr, self._micro)
         self.graph.replay()
         return self.loss
 

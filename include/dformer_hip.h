@@ -750,6 +750,38 @@ int dfm_adamw_amp(long n, float* p, const float* g, float* m, float* v, const fl
                   void* copy, int copy_dtype, dfm_stream_t stream);
 int dfm_loss_scale_update(float* amp, int* flag, float growth, float backoff, int interval, dfm_stream_t stream);
 
+/* ---- optimizer options (csrc/optim.hip): gradient accumulation, global-norm clipping, weight EMA.
+ * What a step decides is read on the device, so one captured graph serves every micro-step:
+ *   win[2]  int32 {micro_index, accum_steps}; a kernel taking `win` does nothing unless
+ *           micro_index == accum_steps - 1 (NULL: no window, always the last micro-step)
+ *   clip_state[2]  float32 {total_norm, coef}
+ * dfm_grad_accumulate: acc += g, the `p.grad += g` of a backward without zero_grad(). The update that
+ * consumes acc writes zero back, so there is no first-micro-step variant and no memset. */
+int dfm_grad_accumulate(long n, float* acc, const float* g, dfm_stream_t stream);
+/* torch.nn.utils.clip_grad_norm_'s norm in two stages with a fixed summation order (no atomics).
+ * dfm_grad_sumsq writes dfm_grad_sumsq_blocks() float32 partials of sum g^2 to `part` (one call per
+ * flat buffer, each into its own slice of one partial buffer; n = 0 writes zeros). With `flag` it
+ * is also dfm_grad_nonfinite over the same read (flag[0] = 1 on inf / nan; not cleared). */
+int dfm_grad_sumsq_blocks(void);
+int dfm_grad_sumsq(long n, const float* g, float* part, int* flag, const int* win, dfm_stream_t stream);
+/* One block over the npart partials of every buffer, summed in double:
+ *   total_norm = sqrt(sum) * grad_scale (/ amp[0], the loss scale, when amp is given)
+ *   coef = min(1, max_norm / (total_norm + 1e-6)), NaN when the norm is NaN (torch.clamp). */
+int dfm_grad_clip_coef(int npart, const float* part, float grad_scale, const float* amp, float max_norm,
+                       float* clip_state, const int* win, dfm_stream_t stream);
+/* dfm_adamw_dev / dfm_adamw_amp (amp and flag both given or both NULL) with the options, each off
+ * when its pointer is NULL and then bit-identical to those: the gradient times clip_state[1]
+ * (clip_grad_norm_'s in-place scaling); no write unless win says last micro-step; ema = ema_decay *
+ * ema + (1 - ema_decay) * p_new in the same pass (ema.lerp_(p, 1 - decay) after optimizer.step());
+ * clear_g: g is the accumulation buffer and is zeroed once consumed, also by a step that flag skips. */
+int dfm_adamw_opt(long n, float* p, float* g, int clear_g, float* m, float* v, const float* hyper,
+                  const float* amp, const int* flag, const float* clip_state, const int* win, float* ema,
+                  float ema_decay, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
+                  void* copy, int copy_dtype, dfm_stream_t stream);
+/* dfm_loss_scale_update once per accumulation window (GradScaler.update after the window's step). */
+int dfm_loss_scale_update_win(float* amp, int* flag, float growth, float backoff, int interval, const int* win,
+                              dfm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
