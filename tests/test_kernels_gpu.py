@@ -1,4 +1,6 @@
-"""Numerics of every HIP kernel against a plain PyTorch fp32 reference of the same op (GPU)."""
+"""Numerics of the HIP entry points against a plain PyTorch fp32 reference of the same op (GPU), at
+hand-picked shapes. Which kernel instantiation a shape runs is not checked here: the cases of
+test_kernel_variants_gpu.py pin the instantiations by name against fp64 references."""
 import math
 
 import pytest
