@@ -85,12 +85,18 @@ _SIGS = {
     "dfm_layernorm_bwd_workspace": (c_size_t, [c_long, c_int]),
     "dfm_layernorm_bwd": (c_int, [c_int, c_long, c_int, P, c_long, P, c_long, P, P, P, P, c_long, P, c_long, c_int,
                                   P, P, P, P, P]),
+    "dfm_layernorm_bwd_pool": (c_int, [c_int, c_long, c_int, P, c_long, P, c_long, P, P, P, P, c_long, P, c_long, c_int,
+                                       P, P, P, P, P, c_long, c_int, c_int, c_int, P]),
     "dfm_residual_bwd_workspace": (c_size_t, [c_long, c_int]),
     "dfm_residual_bwd": (c_int, [c_int, c_long, c_int, P, c_long, P, c_long, P, P, c_long, P, c_long, P, P, P, P]),
+    "dfm_residual_bwd2": (c_int, [c_int] + [c_long, c_int, P, c_long, P, c_long, P, P, c_long, P, c_long, P, P, P] * 2 +
+                          [P]),
     "dfm_dwconv_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P, P, c_int, P, c_long, P, c_long,
                                P]),
     "dfm_dwconv_bwd_data": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_int, P, c_long,
                                     c_int, P]),
+    "dfm_dwconv_bwd_data_mul": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_int, P, c_long, P,
+                                        c_long, P, c_long, P]),
     "dfm_dwconv_bwd_weight_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "dfm_dwconv_bwd_weight": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P, P, P, P,
                                       P]),
@@ -130,6 +136,8 @@ _SIGS = {
     "dfm_dual_mul": (c_int, [c_int, c_long, c_int, P, c_long, P, c_long, P, c_long, P, c_long, P, c_long, P]),
     "dfm_adaptive_pool7_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, P]),
     "dfm_adaptive_pool7_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, c_int, P]),
+    "dfm_adaptive_pool7_fwd2": (c_int, [c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, c_int, P, c_long, P,
+                                        c_long, P]),
     "dfm_bilinear_fwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, c_int, P]),
     "dfm_bilinear_bwd": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, c_long, P, c_long, c_int, P]),
     "dfm_pooled_attn_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -8,11 +8,10 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "pool7.h"
 
 namespace {
-// ------------------------------------------------------------------ adaptive average pool 7x7
-DFM_INLINE int bin_lo(int i, int n) { return (i * n) / 7; }
-DFM_INLINE int bin_hi(int i, int n) { return ((i + 1) * n + 6) / 7; }
+// ------------------------------------------------------------------ adaptive average pool 7x7 (bins: pool7.h)
 
 template <typename T>
 __global__ void pool7_fwd_kernel(int B, int H, int W, int C, const T* __restrict__ x, long ldx, T* __restrict__ y,
@@ -130,12 +129,29 @@ __global__ void bilinear_bwd_kernel(int B, int Hi, int Wi, int Ho, int Wo, int C
 inline bool vec_ok(int C, const void* p, long ld) { return C % 8 == 0 && ld % 8 == 0 && (uintptr_t)p % 16 == 0; }
 
 // pool: one block per (image, cell); CV = C/8 lanes per pixel, 256/CV pixels of the bin in
-// flight, partial sums meet in LDS in a fixed order.
+// flight, partial sums meet in LDS in a fixed order. A launch carries up to two problems over the same
+// B, H, W (by value): blocks [0, 49 B) pool the first, [49 B, 98 B) the second.
+struct Pool7Problem {
+  const void* x;
+  long ldx;
+  void* y;
+  long ldy;
+  int C;
+};
+struct Pool7Args {
+  Pool7Problem p[2];
+};
 template <typename T>
-__global__ __launch_bounds__(256) void pool7_fwd_vec_kernel(int B, int H, int W, int C, const T* __restrict__ x,
-                                                            long ldx, T* __restrict__ y, long ldy) {
+__global__ __launch_bounds__(256) void pool7_fwd_vec_kernel(int B, int H, int W, Pool7Args a) {
   extern __shared__ float pred[];  // [PG][C]
-  const int cell = blockIdx.x % 49, b = blockIdx.x / 49;
+  const bool second = (int)blockIdx.x >= 49 * B;  // uniform over the block
+  const Pool7Problem P = second ? a.p[1] : a.p[0];
+  const int bid = second ? (int)blockIdx.x - 49 * B : (int)blockIdx.x;
+  const int C = P.C;
+  const T* __restrict__ x = (const T*)P.x;
+  T* __restrict__ y = (T*)P.y;
+  const long ldx = P.ldx, ldy = P.ldy;
+  const int cell = bid % 49, b = bid / 49;
   const int CV = C / 8, PG = 256 / CV;
   const int cv = threadIdx.x % CV, pg = threadIdx.x / CV;
   const int i = cell / 7, j = cell % 7;
@@ -172,24 +188,8 @@ __global__ void pool7_bwd_vec_kernel(int B, int H, int W, int C, const T* __rest
     const int c = (int)(e % CV) * 8;
     const long pix = e / CV;
     const int w = pix % W, h = (pix / W) % H, b = pix / ((long)W * H);
-    float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    // for n >= 7 a row lies in bins ic-1..ic+1 only; smaller maps repeat rows over more bins
-    const int ic = (h * 7) / H, jc = (w * 7) / W;
-    const int ia = H >= 7 ? max(0, ic - 1) : 0, ib = H >= 7 ? min(6, ic + 1) : 6;
-    const int ja = W >= 7 ? max(0, jc - 1) : 0, jb = W >= 7 ? min(6, jc + 1) : 6;
-    for (int i = ia; i <= ib; ++i) {
-      const int ha = bin_lo(i, H), hb = bin_hi(i, H);
-      if (h < ha || h >= hb) continue;
-      for (int j = ja; j <= jb; ++j) {
-        const int wa = bin_lo(j, W), wb = bin_hi(j, W);
-        if (w < wa || w >= wb) continue;
-        const float inv = 1.f / (float)((hb - ha) * (wb - wa));
-        float v[8];
-        ld8<T>(dy + ((long)b * 49 + i * 7 + j) * lddy + c, v);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) s[q] += v[q] * inv;
-      }
-    }
+    float s[8];
+    pool7_gather<T, 8>(dy, lddy, b, h, w, H, W, c, s);
     T* p = dx + pix * lddx + c;
     if (accumulate) {
       float o[8];
@@ -1056,6 +1056,7 @@ __global__ void head_repack4_kernel(int n4, int heads, int q4s, int ls4, int q4d
 }
 
 unsigned grid_for(long n) { return (unsigned)min((long)8192, max(1L, (n + 255) / 256)); }
+size_t pool7_lds(int C) { return (size_t)(256 / (C / 8)) * C * sizeof(float); }
 }  // namespace
 
 extern "C" int dfm_adaptive_pool7_fwd(int dtype, int B, int H, int W, int C, const void* x, long ldx, void* y,
@@ -1063,10 +1064,9 @@ extern "C" int dfm_adaptive_pool7_fwd(int dtype, int B, int H, int W, int C, con
   DFM_CHECK_DTYPE(dtype);
   hipStream_t s = (hipStream_t)stream;
   if (C <= 2048 && vec_ok(C, x, ldx)) {
-    const size_t lds = (size_t)(256 / (C / 8)) * C * sizeof(float);
-    DFM_DTYPE_SWITCH(dtype, T,
-                     DFM_LAUNCH(pool7_fwd_vec_kernel<T>, dim3(B * 49), dim3(256), lds, s, B, H, W, C, (const T*)x, ldx,
-                                (T*)y, ldy));
+    Pool7Args a{};
+    a.p[0] = Pool7Problem{x, ldx, y, ldy, C};
+    DFM_DTYPE_SWITCH(dtype, T, DFM_LAUNCH(pool7_fwd_vec_kernel<T>, dim3(B * 49), dim3(256), pool7_lds(C), s, B, H, W, a));
   } else {
     dim3 grid(B * 49, cdiv(C, 256));
     DFM_DTYPE_SWITCH(dtype, T,
@@ -1074,6 +1074,27 @@ extern "C" int dfm_adaptive_pool7_fwd(int dtype, int B, int H, int W, int C, con
   }
   DFM_LAUNCH_CHECK();
   return DFM_OK;
+}
+
+extern "C" int dfm_adaptive_pool7_fwd2(int dtype, int B, int H, int W, int C1, const void* x1, long ldx1, void* y1,
+                                       long ldy1, int C2, const void* x2, long ldx2, void* y2, long ldy2,
+                                       dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  DFM_CHECK_ARG(x1 && y1 && x2 && y2 && B > 0 && H > 0 && W > 0 && C1 > 0 && C2 > 0 && (long)B * 98 <= 0x7fffffffL,
+                "dfm_adaptive_pool7_fwd2: bad argument");
+  if (C1 <= 2048 && C2 <= 2048 && vec_ok(C1, x1, ldx1) && vec_ok(C2, x2, ldx2)) {
+    Pool7Args a{};
+    a.p[0] = Pool7Problem{x1, ldx1, y1, ldy1, C1};
+    a.p[1] = Pool7Problem{x2, ldx2, y2, ldy2, C2};
+    const size_t lds = std::max(pool7_lds(C1), pool7_lds(C2));  // dynamic LDS for the larger problem
+    DFM_DTYPE_SWITCH(dtype, T, DFM_LAUNCH(pool7_fwd_vec_kernel<T>, dim3(B * 98), dim3(256), lds, (hipStream_t)stream, B,
+                                          H, W, a));
+    DFM_LAUNCH_CHECK();
+    return DFM_OK;
+  }
+  // off the vector path: the two launches dfm_adaptive_pool7_fwd issues
+  const int rc = dfm_adaptive_pool7_fwd(dtype, B, H, W, C1, x1, ldx1, y1, ldy1, stream);
+  return rc != DFM_OK ? rc : dfm_adaptive_pool7_fwd(dtype, B, H, W, C2, x2, ldx2, y2, ldy2, stream);
 }
 
 extern "C" int dfm_adaptive_pool7_bwd(int dtype, int B, int H, int W, int C, const void* dy, long lddy, void* dx,

@@ -201,6 +201,27 @@ void residual_bwd(Run& r, long rows, int C, V dout, V f, const float* ls, const 
                           r.s));
 }
 
+// the depth LayerNorm's backward with the pooled-query gradient (dpooled's last C columns) gathered in its dy load
+void layernorm_bwd_pool(Run& r, int B, int H, int W, int C, V x, V dy, const float* g, const float* mu, const float* rs, V dres,
+                        V dx, float* dg, float* db, V pooled) {
+  const long rows = (long)B * H * W;
+  void* ws = r.scr(dfm_layernorm_bwd_workspace(rows, C));
+  if (r.live())
+    r.ok(dfm_layernorm_bwd_pool(r.dt, rows, C, x.p, x.ld, dy.p, dy.ld, g, mu, rs, dres.p, dres.ld, dx.p, dx.ld, 0, dg, db,
+                                ws, nullptr, pooled.p, pooled.ld, B, H, W, r.s));
+}
+// two residual backwards (the attention's proj / proj_e pair) in one launch
+void residual_bwd2(Run& r, long rows, int C1, V dout1, V f1, const float* ls1, const float* rowscale1, V df1,
+                   float* dls1, int C2, V dout2, V f2, const float* ls2, const float* rowscale2, V df2, float* dls2,
+                   long rps) {
+  const size_t w1 = dfm_residual_bwd_workspace(rows, C1), w2 = dfm_residual_bwd_workspace(rows, C2);
+  char* ws = static_cast<char*>(r.scr(w1 + w2));
+  if (r.live())
+    r.ok(dfm_residual_bwd2(r.dt, rows, C1, dout1.p, dout1.ld, f1.p, f1.ld, ls1, rowscale1, rps, df1.p, df1.ld, dls1, ws,
+                           nullptr, rows, C2, dout2.p, dout2.ld, f2.p, f2.ld, ls2, rowscale2, rps, df2.p, df2.ld, dls2,
+                           ws + w1, nullptr, r.s));
+}
+
 struct FfnSaved {  // what a ConvFFN's forward keeps for its backward
   V xn, h, f, gp, g;  // gp = GELU'(hpre), g = GELU(hpre): the op-level chain only
   float* mean = nullptr;
@@ -439,10 +460,9 @@ void block_fwd(Run& r, const Dims& m, const BlockIO& io, V y, V ye) {
   }
   if (m.window) {  // softmax(q_pool k^T) v over the 7 x 7 pooled queries, upsampled into f[:, C:C+Ch]
     const int B = m.sh.B;
-    if (r.live())
-      r.ok(dfm_adaptive_pool7_fwd(r.dt, B, m.sh.H, m.sh.W, C, s.xn.p, s.xn.ld, s.pooled.p, s.pooled.ld, r.s));
-    if (r.live())
-      r.ok(dfm_adaptive_pool7_fwd(r.dt, B, m.sh.H, m.sh.W, Ch, s.xen.p, s.xen.ld, s.pooled.col(C).p, s.pooled.ld, r.s));
+    if (r.live())  // pool(LN x) | pool(LN_e xe) into pooled's two column blocks, one launch
+      r.ok(dfm_adaptive_pool7_fwd2(r.dt, B, m.sh.H, m.sh.W, C, s.xn.p, s.xn.ld, s.pooled.p, s.pooled.ld, Ch, s.xen.p,
+                                   s.xen.ld, s.pooled.col(C).p, s.pooled.ld, r.s));
     linear(r, s.pooled, (long)B * 49, C + Ch, p[DFM_BP_SC_W], Ch, F(p, DFM_BP_SC_B), s.m);
     void* ws = r.scr(dfm_pooled_attn_workspace(B, m.heads, (int)(P / B), m.dhd));
     if (r.live())
@@ -489,7 +509,11 @@ void block_bwd(Run& r, const Dims& m, const BlockIO& io, V dy, V dye, V dx, V dx
   // proj / proj_e: one weight-gradient GEMM each, one input-gradient GEMM over [dp1 | dp1e] when the
   // two weights are stacked in memory
   V dpc = r.temp(P, C + Ch);
-  residual_bwd(r, P, C, dx1, s.p1, F(p, DFM_BP_LS1), io.rs[0], rps, dpc, gr[DFM_BP_LS1]);
+  if (m.drop_depth)
+    residual_bwd(r, P, C, dx1, s.p1, F(p, DFM_BP_LS1), io.rs[0], rps, dpc, gr[DFM_BP_LS1]);
+  else  // proj and proj_e as one launch
+    residual_bwd2(r, P, C, dx1, s.p1, F(p, DFM_BP_LS1), io.rs[0], dpc, gr[DFM_BP_LS1], Ch, dxe1, s.p1e,
+                  F(p, DFM_BP_LS1E), io.rs[2], dpc.col(C), gr[DFM_BP_LS1E], rps);
   wgrad(r, dpc, P, C, s.f, fw, gr[DFM_BP_PROJ_W], gr[DFM_BP_PROJ_B]);
   // the projections' input gradient df = dpc [Wp; Wpe] (one GEMM when the two weights are stacked in
   // memory, or Wp alone with drop_depth) by its column blocks f = cat(q * a, attn, cx * xe'), the two
@@ -497,10 +521,7 @@ void block_bwd(Run& r, const Dims& m, const BlockIO& io, V dy, V dye, V dx, V dx
   // dxe' = df_e cx; df is only materialised for the attention block (or, with separate weights, whole)
   const bool stacked = m.drop_depth || adjacent(p[DFM_BP_PROJ_W], (size_t)C * fw * es, p[DFM_BP_PROJE_W]);
   const long Kp = m.drop_depth ? C : C + Ch;
-  if (!m.drop_depth) {
-    residual_bwd(r, P, Ch, dxe1, s.p1e, F(p, DFM_BP_LS1E), io.rs[2], rps, dpc.col(C), gr[DFM_BP_LS1E]);
-    wgrad(r, dpc.col(C), P, Ch, s.f, fw, gr[DFM_BP_PROJE_W], gr[DFM_BP_PROJE_B]);
-  }
+  if (!m.drop_depth) wgrad(r, dpc.col(C), P, Ch, s.f, fw, gr[DFM_BP_PROJE_W], gr[DFM_BP_PROJE_B]);
   V q = s.qcl, cx = s.qcl.col(C), g = s.qcl.col(C + Ch);
   V dqcl = r.temp(P, 2 * C + Ch);
   V dq = dqcl, dcx = dqcl.col(C), dl = dqcl.col(C + Ch);
@@ -577,13 +598,9 @@ void block_bwd(Run& r, const Dims& m, const BlockIO& io, V dy, V dye, V dx, V dx
       r.ok(dfm_dwconv_bwd_weight(r.dt, B, m.sh.H, m.sh.W, C, 7, g.p, g.ld, dapre.p, dapre.ld, gr[DFM_BP_CONV_W],
                                  gr[DFM_BP_CONV_B], ws, nullptr, r.s));
   }
-  if (r.live())
-    r.ok(dfm_dwconv_bwd_data(r.dt, B, m.sh.H, m.sh.W, C, 7, dapre.p, dapre.ld, F(p, DFM_BP_CONV_W), 0, dg.p, dg.ld,
-                             m.window ? 1 : 0, r.s));
-  if (r.live())  // lpre holds GELU'(l pre-activation)
-    r.ok(dfm_scale_mul(r.dt, P, C, dg.p, dg.ld, s.lpre.p, s.lpre.ld, nullptr, nullptr, 1, 1.f, dl.p, dl.ld, 0, r.s));
-  if (m.window && r.live())
-    r.ok(dfm_adaptive_pool7_bwd(r.dt, B, m.sh.H, m.sh.W, Ch, dpooled.col(C).p, dpooled.ld, dxen.p, dxen.ld, 1, r.s));
+  if (r.live())  // dl = (DW7 input gradient (+ dg, the kv input gradient)) * lpre, lpre = GELU'(l pre-activation)
+    r.ok(dfm_dwconv_bwd_data_mul(r.dt, B, m.sh.H, m.sh.W, C, 7, dapre.p, dapre.ld, F(p, DFM_BP_CONV_W), 0,
+                                 m.window ? dg.p : nullptr, dg.ld, s.lpre.p, s.lpre.ld, dl.p, dl.ld, r.s));
   // q | q_cut | l
   const bool one_w = adjacent(p[DFM_BP_Q_W], (size_t)C * C * es, p[DFM_BP_QCUT_W]) &&
                      adjacent(p[DFM_BP_QCUT_W], (size_t)Ch * C * es, p[DFM_BP_L_W]);
@@ -598,8 +615,12 @@ void block_bwd(Run& r, const Dims& m, const BlockIO& io, V dy, V dye, V dx, V dx
     dgrad(r, dl, P, C, p[DFM_BP_L_W], C, dxn, true);
   }
   layernorm_bwd(r, P, C, io.x, dxn, F(p, DFM_BP_NORM_W), s.mu1, s.rs1, dx1, dx, gr[DFM_BP_NORM_W], gr[DFM_BP_NORM_B]);
-  layernorm_bwd(r, P, Ch, io.xe, dxen, F(p, DFM_BP_NORM_E_W), s.mu2, s.rs2, dxe1, dxe, gr[DFM_BP_NORM_E_W],
-                gr[DFM_BP_NORM_E_B]);
+  if (m.window)  // the pooled queries' x_e columns flow back inside the LayerNorm backward's dy load
+    layernorm_bwd_pool(r, B, m.sh.H, m.sh.W, Ch, io.xe, dxen, F(p, DFM_BP_NORM_E_W), s.mu2, s.rs2, dxe1, dxe, gr[DFM_BP_NORM_E_W],
+                       gr[DFM_BP_NORM_E_B], dpooled.col(C));
+  else
+    layernorm_bwd(r, P, Ch, io.xe, dxen, F(p, DFM_BP_NORM_E_W), s.mu2, s.rs2, dxe1, dxe, gr[DFM_BP_NORM_E_W],
+                  gr[DFM_BP_NORM_E_B]);
 }
 
 // whether the Block described by m has parameter DFM_BP_i (kv / short_cut_linear need the window; proj_e,

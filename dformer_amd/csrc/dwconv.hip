@@ -103,7 +103,9 @@ __global__ __launch_bounds__(256) void dw_tile_fwd_kernel(int B, int H, int W, i
                                                           const T* __restrict__ x, long ldx,
                                                           const float* __restrict__ w, const float* __restrict__ bias,
                                                           int add_identity, T* __restrict__ y, long ldy,
-                                                          int accumulate, T* __restrict__ gout, long ldg) {
+                                                          int accumulate, T* __restrict__ gout, long ldg,
+                                                          const T* prior, long ldprior, const T* __restrict__ mul,
+                                                          long ldmul) {
   constexpr int CPT = DwCfg<T>::CPT, R = K / 2;
   constexpr int TWS = DwFwdTile<T, K, VAR>::TWS, STRIPS = DwFwdTile<T, K, VAR>::STRIPS;
   constexpr int TH = 256 / (NG * STRIPS), TWT = TWS * STRIPS;
@@ -210,6 +212,18 @@ __global__ __launch_bounds__(256) void dw_tile_fwd_kernel(int B, int H, int W, i
       ldv<T>(yp, o);
 #pragma unroll
       for (int e = 0; e < CPT; ++e) acc[t][e] += o[e];
+    }
+    if (prior) {  // accumulate onto another tensor than y (it may be y: read here, before this pixel's store)
+      float o[CPT];
+      ldv<T>(prior + p * ldprior + c0, o);
+#pragma unroll
+      for (int e = 0; e < CPT; ++e) acc[t][e] += o[e];
+    }
+    if (mul) {  // y = round_T(round_T(acc) * mul): the store and the scale_mul pass of the unfused pair, the
+      float m[CPT];  // product in fp32 and its rounding kept apart
+      ldv<T>(mul + p * ldmul + c0, m);
+#pragma unroll
+      for (int e = 0; e < CPT; ++e) acc[t][e] = Num<T>::to_f(Num<T>::from_f(acc[t][e])) * m[e];
     }
     if (gout) {  // GELU output; y holds the pre-activation or (flag 2) its GELU derivative
       float gv[CPT], dv[CPT];
@@ -1774,7 +1788,8 @@ bool dw_aligned(int C, const void* p, long ld) {
 
 template <typename T, int K, bool FLIP, int NG, int VAR = 0>
 int dw_tile_launch(int B, int H, int W, int C, const void* x, long ldx, const float* w, const float* bias, int id,
-                   void* y, long ldy, int acc, void* gout, long ldg, hipStream_t s) {
+                   void* y, long ldy, int acc, void* gout, long ldg, hipStream_t s, const void* prior = nullptr,
+                   long ldprior = 0, const void* mul = nullptr, long ldmul = 0) {
   constexpr int CPT = DwCfg<T>::CPT, TWS = DwFwdTile<T, K, VAR>::TWS, STRIPS = DwFwdTile<T, K, VAR>::STRIPS;
   constexpr int TH = 256 / (NG * STRIPS), TWT = TWS * STRIPS;
   const int tiles_h = (H + TH - 1) / TH, tiles_w = (W + TWT - 1) / TWT;
@@ -1790,26 +1805,33 @@ int dw_tile_launch(int B, int H, int W, int C, const void* x, long ldx, const fl
     }
   }
   DFM_LAUNCH((dw_tile_fwd_kernel<T, K, FLIP, NG, VAR>), grid, dim3(256), lds, s, B, H, W, C, tiles_h, tiles_w,
-                     (const T*)x, ldx, w, bias, id, (T*)y, ldy, acc, (T*)gout, ldg);
+                     (const T*)x, ldx, w, bias, id, (T*)y, ldy, acc, (T*)gout, ldg, (const T*)prior, ldprior,
+                     (const T*)mul, ldmul);
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }
 
 template <typename T, bool FLIP>
 int dw_fwd(int B, int H, int W, int C, int k, const void* x, long ldx, const float* w, const float* bias, int id,
-           void* y, long ldy, int acc, void* gout, long ldg, hipStream_t s) {
-  DFM_CHECK_ARG(dw_aligned<T>(C, x, ldx) && dw_aligned<T>(C, y, ldy) && (!gout || dw_aligned<T>(C, gout, ldg)),
+           void* y, long ldy, int acc, void* gout, long ldg, hipStream_t s, const void* prior = nullptr,
+           long ldprior = 0, const void* mul = nullptr, long ldmul = 0) {
+  DFM_CHECK_ARG(dw_aligned<T>(C, x, ldx) && dw_aligned<T>(C, y, ldy) && (!gout || dw_aligned<T>(C, gout, ldg)) &&
+                    (!prior || dw_aligned<T>(C, prior, ldprior)) && (!mul || dw_aligned<T>(C, mul, ldmul)),
                 "dwconv: C, row strides and pointers must be 16-byte vector aligned");
   DFM_CHECK_ARG(k == 3 || k == 7, "dwconv: k=%d unsupported", k);
+  const bool fold = prior || mul;  // the folded epilogue lives in the tiled kernel only
   // streaming 3x3 up to 65,536-pixel planes: with its buffer-addressed loads (round 6) it also wins on
   // DFormer-Large's 133x183 stage-0 planes (config 5: 274.1 / 275.7 -> 276.6 / 279.5 images/s; DFormer-B
   // and -Tiny, whose stage-0 ConvFFN forward is the fused kernel, within noise). Round 4 had the LDS-tiled
   // kernel ahead on 120x160 (302 vs 328 us at 512 channels, profiles/r04_dw3_geom_sweep.txt).
   const long plane = (long)H * W;
-  if (k == 3 && plane <= 65536) return f3_launch<T, FLIP>(B, H, W, C, x, ldx, w, bias, id, y, ldy, acc, gout, ldg, s);
+  if (k == 3 && plane <= 65536 && !fold)
+    return f3_launch<T, FLIP>(B, H, W, C, x, ldx, w, bias, id, y, ldy, acc, gout, ldg, s);
   const int G = C / DwCfg<T>::CPT;
   // channel groups per block: as many as the tile geometry allows without idling lanes
-#define GO(KK, NGV) return dw_tile_launch<T, KK, FLIP, NGV>(B, H, W, C, x, ldx, w, bias, id, y, ldy, acc, gout, ldg, s)
+#define GO(KK, NGV)                                                                                              \
+  return dw_tile_launch<T, KK, FLIP, NGV>(B, H, W, C, x, ldx, w, bias, id, y, ldy, acc, gout, ldg, s, prior, ldprior, \
+                                          mul, ldmul)
   if (k == 3) {
     // 64-channel groups (whole 128-byte lines per pixel) on the 120x160 planes: 297-300 vs 307 us at
     // 512 channels, 128-129 vs 138 at 256 (4 x 32 tiles; 16 x 16 tiles with 8 outputs per thread
@@ -1845,6 +1867,20 @@ extern "C" int dfm_dwconv_bwd_data(int dtype, int B, int H, int W, int C, int k,
   DFM_CHECK_ARG(dy && w && dx && B > 0 && H > 0 && W > 0 && C > 0, "dfm_dwconv_bwd_data: bad argument");
   DFM_DTYPE_SWITCH(dtype, T, return dw_fwd<T, true>(B, H, W, C, k, dy, lddy, w, nullptr, add_identity, dx, lddx,
                                                     accumulate, nullptr, 0, (hipStream_t)stream));
+}
+
+extern "C" int dfm_dwconv_bwd_data_mul(int dtype, int B, int H, int W, int C, int k, const void* dy, long lddy,
+                                       const float* w, int add_identity, const void* prior, long ldprior,
+                                       const void* mul, long ldmul, void* dx, long lddx, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  DFM_CHECK_ARG(dy && w && dx && mul && B > 0 && H > 0 && W > 0 && C > 0, "dfm_dwconv_bwd_data_mul: bad argument");
+  DFM_CHECK_ARG(dx != dy && dx != mul, "dfm_dwconv_bwd_data_mul: dx must not be dy or mul");
+  // the streaming 3x3 kernel adds the identity between its taps, the tiled one after them: only without it are
+  // the two bit-identical, and the fold runs in the tiled kernel
+  DFM_CHECK_ARG(!(k == 3 && (long)H * W <= 65536 && (add_identity & 1)),
+                "dfm_dwconv_bwd_data_mul: k = 3 with add_identity is served from 65,537-pixel planes on");
+  DFM_DTYPE_SWITCH(dtype, T, return dw_fwd<T, true>(B, H, W, C, k, dy, lddy, w, nullptr, add_identity & 1, dx, lddx, 0,
+                                                    nullptr, 0, (hipStream_t)stream, prior, ldprior, mul, ldmul));
 }
 
 extern "C" size_t dfm_dwconv_bwd_weight_workspace(int B, int H, int W, int C, int k) {

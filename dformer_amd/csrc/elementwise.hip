@@ -1177,16 +1177,42 @@ extern "C" int dfm_loss_scale_update(float* amp, int* flag, float growth, float 
 // ================================================================ residual / layer-scale backward
 namespace {
 constexpr int RES_BLOCKS = 512;
+constexpr int RES_UNROLL = 4;  // rows of a thread's sequence whose loads are issued before the first use
+
+// One residual problem; a launch carries up to two (blocks [0, p[0].nblk) and [p[0].nblk, ...)), by value.
+struct ResProblem {
+  long rows;
+  const void *dout, *f;
+  long ldo, ldf;
+  const float *colscale, *rowscale;
+  long rps;
+  void* df;
+  long lddf;
+  float* part;
+  int C, nblk;
+};
+struct ResArgs {
+  ResProblem p[2];
+};
 
 // One pass over dout and f: df = dout * colscale * rowscale (written) and per-block partial column
 // sums of dout * f * rowscale. Thread layout: 8 consecutive columns per thread (16-byte vectors for
-// bf16), TPR = C/8 threads per row, 256/TPR rows in flight per block.
+// bf16), TPR = C/8 threads per row, 256/TPR rows per block step. A thread's rows are r0 + rl, + RL, ...
+// in that order (the partials depend on it); RES_UNROLL of them are loaded before the first is used, so
+// a thread has 8 x 16 bytes in flight instead of 2 (the kernel was latency-bound at 2.2 TB/s). The
+// products are written out in the association the one-row loop compiled to: (dout * f) rounded, then one
+// fma with the row scale; (dout * colscale) * rowscale.
 template <typename T>
-__global__ __launch_bounds__(256) void residual_bwd_kernel(long rows, int C, const T* __restrict__ dout, long ldo,
-                                                           const T* __restrict__ f, long ldf_,
-                                                           const float* __restrict__ colscale,
-                                                           const float* __restrict__ rowscale, long rps,
-                                                           T* __restrict__ df, long lddf, float* __restrict__ part) {
+__global__ __launch_bounds__(256) void residual_bwd_kernel(ResArgs a) {
+  const bool second = (int)blockIdx.x >= a.p[0].nblk;  // uniform over the block
+  const ResProblem P = second ? a.p[1] : a.p[0];
+  const int bid = second ? (int)blockIdx.x - a.p[0].nblk : (int)blockIdx.x;
+  const int C = P.C;
+  const T* __restrict__ dout = (const T*)P.dout;
+  const T* __restrict__ f = (const T*)P.f;
+  T* __restrict__ df = (T*)P.df;
+  const float* __restrict__ rowscale = P.rowscale;
+  const long ldo = P.ldo, ldf_ = P.ldf, lddf = P.lddf, rps = P.rps;
   const int TPR = C / 8;
   const int RL = 256 / TPR;
   const int tc = threadIdx.x % TPR, rl = threadIdx.x / TPR;
@@ -1194,21 +1220,58 @@ __global__ __launch_bounds__(256) void residual_bwd_kernel(long rows, int C, con
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   float cs[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) cs[e] = colscale ? colscale[c0 + e] : 1.f;
-  const long per = (rows + gridDim.x - 1) / gridDim.x;
-  const long r0 = (long)blockIdx.x * per, r1 = min(rows, r0 + per);
-  if (rl < RL) {
-    for (long r = r0 + rl; r < r1; r += RL) {
-      const float rs = rowscale ? rowscale[r / rps] : 1.f;
+  for (int e = 0; e < 8; ++e) cs[e] = P.colscale ? P.colscale[c0 + e] : 1.f;
+  const long per = (P.rows + P.nblk - 1) / P.nblk;
+  const long r0 = (long)bid * per, r1 = min(P.rows, r0 + per);
+  if (rl < RL && r0 < r1) {
+    // the row scale's index r / rps: one value for the block where its rows lie in one image (the Block's
+    // shapes), else a 32-bit division per row where the indices allow it
+    const long i0 = r0 / rps;
+    const bool one = (r1 - 1) / rps == i0;
+    const bool small = r1 <= 0x7fffffffL && rps <= 0x7fffffffL;
+    const float rs0 = rowscale ? rowscale[i0] : 1.f;
+    auto scale_of = [&](long r) -> float {
+      if (!rowscale || one) return rs0;
+      return rowscale[small ? (long)((uint32_t)r / (uint32_t)rps) : r / rps];
+    };
+    auto row = [&](const Raw8<T>& dr, const Raw8<T>& fr, float rs, long r) {
       float d[8], fv[8], o[8];
-      ld8<T>(dout + r * ldo + c0, d);
-      ld8<T>(f + r * ldf_ + c0, fv);
+      unpack8(dr, d);
+      unpack8(fr, fv);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        acc[e] += d[e] * fv[e] * rs;
-        o[e] = d[e] * cs[e] * rs;
+        acc[e] = fmaf(d[e] * fv[e], rs, acc[e]);
+        o[e] = (d[e] * cs[e]) * rs;
       }
       st8<T>(df + r * lddf + c0, o);
+    };
+    long r = r0 + rl;
+    for (; r + (long)(RES_UNROLL - 1) * RL < r1; r += (long)RES_UNROLL * RL) {
+      Raw8<T> dr[RES_UNROLL], fr[RES_UNROLL];
+      float rs[RES_UNROLL];
+#pragma unroll
+      for (int u = 0; u < RES_UNROLL; ++u) {
+        const long ru = r + (long)u * RL;
+        dr[u] = ldraw8(dout + ru * ldo + c0);
+        fr[u] = ldraw8(f + ru * ldf_ + c0);
+        rs[u] = scale_of(ru);
+      }
+#pragma unroll
+      for (int u = 0; u < RES_UNROLL; ++u) row(dr[u], fr[u], rs[u], r + (long)u * RL);
+    }
+    if (r < r1) {  // the tail, 1 .. RES_UNROLL - 1 rows: clamped addresses, masked add and store
+      Raw8<T> dr[RES_UNROLL - 1], fr[RES_UNROLL - 1];
+      float rs[RES_UNROLL - 1];
+#pragma unroll
+      for (int u = 0; u < RES_UNROLL - 1; ++u) {
+        const long ru = min(r + (long)u * RL, r1 - 1);
+        dr[u] = ldraw8(dout + ru * ldo + c0);
+        fr[u] = ldraw8(f + ru * ldf_ + c0);
+        rs[u] = scale_of(ru);
+      }
+#pragma unroll
+      for (int u = 0; u < RES_UNROLL - 1; ++u)
+        if (r + (long)u * RL < r1) row(dr[u], fr[u], rs[u], r + (long)u * RL);
     }
   }
   __shared__ float red[256][9];
@@ -1219,8 +1282,44 @@ __global__ __launch_bounds__(256) void residual_bwd_kernel(long rows, int C, con
     const int t = c / 8, e = c % 8;
     float s = 0.f;
     for (int q = 0; q < RL; ++q) s += red[q * TPR + t][e];
-    part[(long)blockIdx.x * C + c] = s;
+    P.part[(long)bid * C + c] = s;
   }
+}
+
+int res_blocks(long rows) { return (int)min((long)RES_BLOCKS, max(1L, rows / 64)); }
+
+// Argument checks of one problem (shared by dfm_residual_bwd and dfm_residual_bwd2).
+int res_check(const char* who, long rows, int C, const void* dout, long lddout, const void* f, long ldf_, const void* df,
+              long lddf, const float* dscale, const void* ws) {
+  DFM_CHECK_ARG(dout && f && df && dscale && ws && C % 8 == 0 && C <= 2048, "%s: bad argument", who);
+  DFM_CHECK_ARG(lddout % 8 == 0 && ldf_ % 8 == 0 && lddf % 8 == 0 && (uintptr_t)dout % 16 == 0 &&
+                    (uintptr_t)f % 16 == 0 && (uintptr_t)df % 16 == 0,
+                "%s: rows must be 16-byte aligned", who);
+  return DFM_OK;
+}
+
+// One launch for the problems of `a` that have rows (p[0] first), then each problem's second stage.
+int res_launch(int dtype, ResArgs a, float* const* dscale, DfmPartialSum* const* defer, hipStream_t s) {
+  if (a.p[0].nblk == 0) {  // only the second problem has rows: it becomes the launch's first
+    a.p[0] = a.p[1];
+    a.p[1].nblk = 0;
+    const int rc = res_launch(dtype, a, dscale + 1, defer + 1, s);
+    return rc;
+  }
+  DFM_DTYPE_SWITCH(dtype, T, DFM_LAUNCH(residual_bwd_kernel<T>, dim3(a.p[0].nblk + a.p[1].nblk), dim3(256), 0, s, a));
+  DFM_LAUNCH_CHECK();
+  for (int q = 0; q < 2; ++q) {
+    if (a.p[q].nblk == 0) continue;
+    const int rc = second_stage(0, a.p[q].nblk, (long)a.p[q].C, a.p[q].part, dscale[q], nullptr, 0L, 0, defer[q], s);
+    if (rc != DFM_OK) return rc;
+  }
+  return DFM_OK;
+}
+
+ResProblem res_problem(long rows, int C, const void* dout, long lddout, const void* f, long ldf_, const float* colscale,
+                       const float* rowscale, long rps, void* df, long lddf, void* ws) {
+  return ResProblem{rows, dout, f, lddout, ldf_, colscale, rowscale, rps > 0 ? rps : 1, df, lddf, (float*)ws, C,
+                    rows > 0 ? res_blocks(rows) : 0};
 }
 }  // namespace
 
@@ -1231,16 +1330,35 @@ extern "C" int dfm_residual_bwd(int dtype, long rows, int C, const void* dout, l
                                 float* dscale, void* ws, DfmPartialSum* defer, dfm_stream_t stream) {
   DFM_CHECK_DTYPE(dtype);
   if (defer) *defer = DfmPartialSum{};
-  DFM_CHECK_ARG(dout && f && df && dscale && ws && C % 8 == 0 && C <= 2048, "dfm_residual_bwd: bad argument");
-  DFM_CHECK_ARG(lddout % 8 == 0 && ldf_ % 8 == 0 && lddf % 8 == 0 && (uintptr_t)dout % 16 == 0 &&
-                    (uintptr_t)f % 16 == 0 && (uintptr_t)df % 16 == 0,
-                "dfm_residual_bwd: rows must be 16-byte aligned");
+  const int rc = res_check("dfm_residual_bwd", rows, C, dout, lddout, f, ldf_, df, lddf, dscale, ws);
+  if (rc != DFM_OK) return rc;
   if (rows == 0) return DFM_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int nblk = (int)min((long)RES_BLOCKS, max(1L, rows / 64));
-  DFM_DTYPE_SWITCH(dtype, T,
-                   DFM_LAUNCH(residual_bwd_kernel<T>, dim3(nblk), dim3(256), 0, s, rows, C, (const T*)dout, lddout,
-                              (const T*)f, ldf_, colscale, rowscale, rps > 0 ? rps : 1, (T*)df, lddf, (float*)ws));
-  DFM_LAUNCH_CHECK();
-  return second_stage(0, nblk, (long)C, (const float*)ws, dscale, nullptr, 0L, 0, defer, s);
+  ResArgs a{};
+  a.p[0] = res_problem(rows, C, dout, lddout, f, ldf_, colscale, rowscale, rps, df, lddf, ws);
+  float* const ds[2] = {dscale, nullptr};
+  DfmPartialSum* const de[2] = {defer, nullptr};
+  return res_launch(dtype, a, ds, de, (hipStream_t)stream);
+}
+
+extern "C" int dfm_residual_bwd2(int dtype, long rows1, int C1, const void* dout1, long lddout1, const void* f1,
+                                 long ldf1, const float* colscale1, const float* rowscale1, long rps1, void* df1,
+                                 long lddf1, float* dscale1, void* ws1, DfmPartialSum* defer1, long rows2, int C2,
+                                 const void* dout2, long lddout2, const void* f2, long ldf2, const float* colscale2,
+                                 const float* rowscale2, long rps2, void* df2, long lddf2, float* dscale2, void* ws2,
+                                 DfmPartialSum* defer2, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  if (defer1) *defer1 = DfmPartialSum{};
+  if (defer2) *defer2 = DfmPartialSum{};
+  int rc = res_check("dfm_residual_bwd2", rows1, C1, dout1, lddout1, f1, ldf1, df1, lddf1, dscale1, ws1);
+  if (rc != DFM_OK) return rc;
+  rc = res_check("dfm_residual_bwd2", rows2, C2, dout2, lddout2, f2, ldf2, df2, lddf2, dscale2, ws2);
+  if (rc != DFM_OK) return rc;
+  DFM_CHECK_ARG(ws1 != ws2, "dfm_residual_bwd2: the two problems need a workspace each");
+  if (rows1 == 0 && rows2 == 0) return DFM_OK;
+  ResArgs a{};
+  a.p[0] = res_problem(rows1, C1, dout1, lddout1, f1, ldf1, colscale1, rowscale1, rps1, df1, lddf1, ws1);
+  a.p[1] = res_problem(rows2, C2, dout2, lddout2, f2, ldf2, colscale2, rowscale2, rps2, df2, lddf2, ws2);
+  float* const ds[2] = {dscale1, dscale2};
+  DfmPartialSum* const de[2] = {defer1, defer2};
+  return res_launch(dtype, a, ds, de, (hipStream_t)stream);
 }

@@ -3,6 +3,7 @@
 // the statistics are exact two-pass values with one read of x. Backward recomputes xhat from
 // the saved mean/rstd and reduces dgamma/dbeta deterministically (per-block partials + sum).
 #include "common.h"
+#include "pool7.h"
 
 namespace {
 constexpr int MAXE = 16;
@@ -226,9 +227,13 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_kernel(long rows, int C, const
                                                          const float* __restrict__ mean,
                                                          const float* __restrict__ rstd, const T* __restrict__ dres,
                                                          long lddres, T* __restrict__ dx, long lddx, int accumulate,
-                                                         float* __restrict__ part) {
+                                                         float* __restrict__ part, const T* __restrict__ pooled,
+                                                         long ldpooled, int H, int W) {
   constexpr int V = LnVec<T>::V;
   constexpr int RPB = 256 / G;
+  // the pooled-gradient fold: not in the 16-bit NV = 4 form, which no call reaches (C <= 1024) and which has
+  // no register to spare
+  constexpr bool FOLD = !(sizeof(T) == 2 && NV == 4);
   const int lg = threadIdx.x % G, grp = threadIdx.x / G;
   const int nvec = C / V;
   float pg[NV][V], pb[NV][V], gw[NV][V];
@@ -260,6 +265,23 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_kernel(long rows, int C, const
       } else {
 #pragma unroll
         for (int e = 0; e < V; ++e) xh[j][e] = g[j][e] = rv[j][e] = 0.f;
+      }
+    }
+    if constexpr (FOLD) {
+      if (pooled) {  // dy += the adaptive pool's backward at this pixel, rounded to T as the separate pass stores it
+        const unsigned pix = (unsigned)row, uw = (unsigned)W, uh = (unsigned)H;  // rows < 2^31 (entry point)
+        const unsigned q = pix / uw;
+        const int w = (int)(pix - q * uw), h = (int)(q % uh), b = (int)(q / uh);
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+          const int vi = j * G + lg;
+          if (vi < nvec) {
+            float sp[V];
+            pool7_gather<T, V>(pooled, ldpooled, b, h, w, H, W, vi * V, sp);
+#pragma unroll
+            for (int e = 0; e < V; ++e) g[j][e] = Num<T>::to_f(Num<T>::from_f(sp[e] + g[j][e]));
+          }
+        }
       }
     }
     float sa = 0.f, sb = 0.f;
@@ -346,6 +368,15 @@ int pick_g(int C) {
 
 constexpr int LN_BWD_BLOCKS = 512;
 
+// whether ln_bwd takes the vector kernels for these operands
+template <typename T>
+bool ln_vec_path(int C, const void* x, long ldx, const void* dy, long lddy, const float* gamma, const void* dres,
+                 long lddres, const void* dx, long lddx) {
+  int VG, VNV;
+  return ln_vec_geom<T>(C, VG, VNV) && ln_al<T>(x, ldx) && ln_al<T>(dy, lddy) && ln_al<T>(dres, lddres) &&
+         ln_al<T>(dx, lddx) && (uintptr_t)gamma % 16 == 0;
+}
+
 template <typename T>
 int ln_fwd(long rows, int C, const void* x, long ldx, const float* gamma, const float* beta, float eps, void* y,
            long ldy, float* mean, float* rstd, hipStream_t s) {
@@ -383,17 +414,17 @@ template <typename T>
 int ln_bwd(long rows, int C, const void* x, long ldx, const void* dy, long lddy, const float* gamma,
            const float* mean, const float* rstd, const void* dres, long lddres, void* dx, long lddx, int acc,
            float* dg, float* db, void* ws, DfmPartialSum* defer,
-           hipStream_t s) {
+           hipStream_t s, const void* pooled = nullptr, long ldpooled = 0, int H = 0, int W = 0) {
   float* part = (float*)ws;
   int VG, VNV;
-  if (ln_vec_geom<T>(C, VG, VNV) && ln_al<T>(x, ldx) && ln_al<T>(dy, lddy) && ln_al<T>(dres, lddres) &&
-      ln_al<T>(dx, lddx) && (uintptr_t)gamma % 16 == 0) {
+  if (ln_vec_path<T>(C, x, ldx, dy, lddy, gamma, dres, lddres, dx, lddx) && ln_vec_geom<T>(C, VG, VNV)) {
     const unsigned vgrid = min((unsigned)LN_BWD_BLOCKS, cdiv(rows, 256 / VG));
     bool launched = false;
 #define GOV(GG, NN)                                                                                            \
   if (!launched && VG == GG && VNV == NN) {                                                                     \
     DFM_LAUNCH((ln_bwd_vec_kernel<T, GG, NN>), dim3(vgrid), dim3(256), 0, s, rows, C, (const T*)x, ldx,   \
-                       (const T*)dy, lddy, gamma, mean, rstd, (const T*)dres, lddres, (T*)dx, lddx, acc, part); \
+                       (const T*)dy, lddy, gamma, mean, rstd, (const T*)dres, lddres, (T*)dx, lddx, acc, part, \
+                       (const T*)pooled, ldpooled, H, W);                                                     \
     launched = true;                                                                                           \
   }
     GOV(4, 1) GOV(8, 1) GOV(16, 1) GOV(32, 1) GOV(64, 1) GOV(64, 2) GOV(64, 4)
@@ -448,4 +479,34 @@ extern "C" int dfm_layernorm_bwd(int dtype, long rows, int C, const void* x, lon
   if (rows == 0) return DFM_OK;
   DFM_DTYPE_SWITCH(dtype, T, return ln_bwd<T>(rows, C, x, ldx, dy, lddy, gamma, mean, rstd, dres, lddres, dx, lddx,
                                               accumulate, dgamma, dbeta, workspace, defer, (hipStream_t)stream));
+}
+
+extern "C" int dfm_layernorm_bwd_pool(int dtype, long rows, int C, const void* x, long ldx, void* dy, long lddy,
+                                      const float* gamma, const float* mean, const float* rstd, const void* dres,
+                                      long lddres, void* dx, long lddx, int accumulate, float* dgamma, float* dbeta,
+                                      void* workspace, DfmPartialSum* defer, const void* pooled, long ldpooled, int B,
+                                      int H, int W, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  if (defer) *defer = DfmPartialSum{};
+  DFM_CHECK_ARG(C > 0 && C <= 1024, "dfm_layernorm_bwd_pool: C=%d unsupported", C);
+  DFM_CHECK_ARG(x && dy && dx && gamma && mean && rstd && dgamma && dbeta && workspace && pooled,
+                "dfm_layernorm_bwd_pool: null argument");
+  DFM_CHECK_ARG(B > 0 && H > 0 && W > 0 && rows == (long)B * H * W && rows <= 0x7fffffffL && dx != dy,
+                "dfm_layernorm_bwd_pool: rows must be B * H * W (below 2^31) and dx another tensor than dy");
+  // the fold needs the vector LayerNorm kernel, and operands for which dfm_adaptive_pool7_bwd takes its vector
+  // kernel too (the scalar one divides by the bin size where the vector one multiplies by its reciprocal)
+  bool fold = C % 8 == 0 && lddy % 8 == 0 && ldpooled % 8 == 0 && (uintptr_t)dy % 16 == 0 && (uintptr_t)pooled % 16 == 0;
+  DFM_DTYPE_SWITCH(dtype, T, {
+    int VG, VNV;
+    fold = fold && ln_vec_path<T>(C, x, ldx, dy, lddy, gamma, dres, lddres, dx, lddx) && ln_vec_geom<T>(C, VG, VNV) &&
+           !(sizeof(T) == 2 && VNV == 4);
+  });
+  if (!fold) {  // off the vector path: the pool's backward onto dy, then the LayerNorm backward, as two launches
+    const int rc = dfm_adaptive_pool7_bwd(dtype, B, H, W, C, pooled, ldpooled, dy, lddy, 1, stream);
+    if (rc != DFM_OK) return rc;
+    pooled = nullptr;
+  }
+  DFM_DTYPE_SWITCH(dtype, T, return ln_bwd<T>(rows, C, x, ldx, dy, lddy, gamma, mean, rstd, dres, lddres, dx, lddx,
+                                              accumulate, dgamma, dbeta, workspace, defer, (hipStream_t)stream, pooled,
+                                              ldpooled, H, W));
 }

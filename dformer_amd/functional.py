@@ -300,6 +300,13 @@ class ConvFFNFn(torch.autograd.Function):
 # branch on a side stream measured 381.6 vs 383.4 images/s and was dropped: it is short and the
 # fork / join costs what the overlap gains; a second backward stream for the pooled-attention
 # branch gained nothing either.)
+#
+# FOLD_BWD_PASSES: the small memory passes at the head and tail of the backward chains run folded into their
+# neighbours, every result bit-identical to the unfolded sequence (False, kept for the bit-equality test and
+# for measuring): proj / proj_e residual backward as one launch (residual_bwd2), the GELU' scale of dl inside
+# the 7x7 input gradient (dwconv_bwd_data_mul), the depth branch's pooled-query gradient inside the depth
+# LayerNorm backward's dy load (layernorm_bwd_pool), and the forward's two pools as one launch (pool7_pair).
+FOLD_BWD_PASSES = True
 
 
 class AttentionFn(torch.autograd.Function):
@@ -351,8 +358,11 @@ class AttentionFn(torch.autograd.Function):
         if window:
             dh = C // heads // 2
             pooled = torch.empty(B * 49, C + Ch, device=dev, dtype=dt)
-            K.pool7(xn, shape, out=pooled[:, :C])
-            K.pool7(xen, shape, out=pooled[:, C:])
+            if FOLD_BWD_PASSES:
+                K.pool7_pair(xn, xen, shape, pooled[:, :C], pooled[:, C:])
+            else:
+                K.pool7(xn, shape, out=pooled[:, :C])
+                K.pool7(xen, shape, out=pooled[:, C:])
             m = K.linear(pooled, wcast(dt, wsc), bsc)
             o, lse = K.pooled_attn(m, kv[:, :Ch], kv[:, Ch:], B, heads, P // B, dh, dh ** -0.5)
             K.bilinear(o, (7, 7), (H, W), B, out=f[:, C:C + Ch])
@@ -413,8 +423,12 @@ class AttentionFn(torch.autograd.Function):
         else:
             dxe1 = dxe1.contiguous()
             dpc = torch.empty(P, C + Ch, device=dev, dtype=dt)
-            _, grads["ls1"] = K.residual_bwd(dx1, p1, ls1, rowscale, rps, df=dpc[:, :C])
-            _, grads["ls1e"] = K.residual_bwd(dxe1, p1e, ls1e, rowscale_e, rps, df=dpc[:, C:])
+            if FOLD_BWD_PASSES:
+                grads["ls1"], grads["ls1e"] = K.residual_bwd2(dx1, p1, ls1, rowscale, rps, dpc[:, :C],
+                                                              dxe1, p1e, ls1e, rowscale_e, rps, dpc[:, C:])
+            else:
+                _, grads["ls1"] = K.residual_bwd(dx1, p1, ls1, rowscale, rps, df=dpc[:, :C])
+                _, grads["ls1e"] = K.residual_bwd(dxe1, p1e, ls1e, rowscale_e, rps, df=dpc[:, C:])
             ow, ob = gslot_rows(wp, wpe), gslot_rows(bp, bpe)
             dWc, dbc = K.linear_wgrad(dpc, f, out=ow, bias_grad=True, bias_out=ob)
             grads["wp"], grads["wpe"] = dWc[:C], dWc[C:]
@@ -468,8 +482,11 @@ class AttentionFn(torch.autograd.Function):
             K.gemm_many(calls)
             ow, ob = gslot(wconv), gslot(bconv)
             grads["wconv"], grads["bconv"] = K.dwconv_bwd_weight(g, dapre, shape, 7, dw=ow, db=ob)
-            K.dwconv_bwd_data(dapre, shape, wconv, 7, dx=dg, accumulate=bool(window))
-            K.scale_mul(dg, mul=lpre, out=dl)  # lpre holds GELU'(l pre-activation)
+            if FOLD_BWD_PASSES:  # the GELU' scale rides in the 7x7 input gradient's store (lpre holds GELU'(l pre))
+                K.dwconv_bwd_data_mul(dapre, shape, wconv, 7, lpre, prior=dg if window else None, dx=dl)
+            else:
+                K.dwconv_bwd_data(dapre, shape, wconv, 7, dx=dg, accumulate=bool(window))
+                K.scale_mul(dg, mul=lpre, out=dl)  # lpre holds GELU'(l pre-activation)
         # the depth branch: cxe = cx * xe',  xe' = e_back(DW7(e_fore(LN_e xe)))
         if drop_depth and dxe1 is not None:  # the Block's x_e output is xe' itself
             K.scale_mul(dxe1.contiguous(), out=dxep, accumulate=True)
@@ -487,7 +504,8 @@ class AttentionFn(torch.autograd.Function):
         dxen = K.linear_dgrad(de1, wcast(dt, wef))
         # side allocations read from here on, or by the block's queued weight gradients
         join(side, made=(dg, dapre, dkv, dpooled, dxn, do, dm))
-        if dpooled is not None:
+        fold_pool = FOLD_BWD_PASSES and dpooled is not None  # the depth LayerNorm backward gathers it itself
+        if dpooled is not None and not fold_pool:
             K.pool7_bwd(dpooled[:, C:], shape, dx=dxen, accumulate=True)
         # q | q_cut | l
         dWqcl, dbqcl = K.linear_wgrad(dqcl, xn, bias_grad=True, out=gslot_rows(wq, wqc, wl),
@@ -500,7 +518,11 @@ class AttentionFn(torch.autograd.Function):
         else:
             K.linear_dgrad(dqcl, Wqcl, out=dxn, accumulate=True)
         dx, grads["n_w"], grads["n_b"] = K.layernorm_bwd(x, dxn, n_w, mu1, rs1, dres=dx1)
-        dxe, grads["ne_w"], grads["ne_b"] = K.layernorm_bwd(xe, dxen, ne_w, mu2, rs2, dres=dxe_res)
+        if fold_pool:
+            dxe, grads["ne_w"], grads["ne_b"] = K.layernorm_bwd_pool(xe, dxen, ne_w, mu2, rs2, dpooled[:, C:], shape,
+                                                                     dres=dxe_res)
+        else:
+            dxe, grads["ne_w"], grads["ne_b"] = K.layernorm_bwd(xe, dxen, ne_w, mu2, rs2, dres=dxe_res)
         out = []
         for name, p in zip(ATTN_PARAM_NAMES, params):
             gr = grads.get(name)

@@ -370,6 +370,44 @@ def layernorm_bwd(x, dy, gamma, mean, rstd, dx=None, accumulate=False, dres=None
     return dx, dg, db
 
 
+def layernorm_bwd_pool(x, dy, gamma, mean, rstd, pooled, shape, dres=None):
+    """layernorm_bwd of dy + pool7_bwd(pooled) (the sum rounded to the dtype, as pool7_bwd(accumulate=True) leaves it
+    in dy): bit-identical to that pair, in one launch where the vector LayerNorm kernel applies (dy is then left
+    as it was; elsewhere the entry point issues the pair and dy receives the sum). Returns (dx, dgamma, dbeta)."""
+    B, H, W = shape
+    rows, C = x.shape
+    dx = torch.empty(rows, C, device=x.device, dtype=x.dtype)
+    dg = torch.empty(C, device=x.device, dtype=torch.float32)
+    db = torch.empty(C, device=x.device, dtype=torch.float32)
+    ws, ps = _red_ws(lib.dfm_layernorm_bwd_workspace(rows, C), x.device)
+    check(lib.dfm_layernorm_bwd_pool(dtype_code(x), rows, C, ptr(x), ld(x), ptr(dy), ld(dy), ptr(gamma), ptr(mean),
+                                     ptr(rstd), ptr(dres), ld(dres) if dres is not None else 0, ptr(dx), ld(dx), 0,
+                                     ptr(dg), ptr(db), ptr(ws), _pref(ps), ptr(pooled), ld(pooled), B, H, W, stream()),
+          "dfm_layernorm_bwd_pool")
+    if ACCOUNT is not None:
+        _acct(0, rows * C * _es(x) * (3 + (dres is not None)) + 8 * rows + B * 49 * C * _es(x))
+    return dx, dg, db
+
+
+def residual_bwd2(dout1, f1, colscale1, rowscale1, rps1, df1, dout2, f2, colscale2, rowscale2, rps2, df2):
+    """Two residual_bwd problems in one launch (the attention backward's proj / proj_e pair): every result
+    bit-identical to two residual_bwd calls. Returns (dls1, dls2)."""
+    prob = []
+    for dout, f, cs, rs, rps, df in ((dout1, f1, colscale1, rowscale1, rps1, df1),
+                                     (dout2, f2, colscale2, rowscale2, rps2, df2)):
+        rows, C = dout.shape
+        dls = torch.empty(C, device=dout.device, dtype=torch.float32)
+        ws, ps = _red_ws(lib.dfm_residual_bwd_workspace(rows, C), dout.device)
+        if ps is None and prob:  # outside a wgrad_group the stream's scratch serves one problem: its own buffer
+            ws = torch.empty(lib.dfm_residual_bwd_workspace(rows, C), dtype=torch.uint8, device=dout.device)
+        prob.append((dls, ps, [rows, C, ptr(dout), ld(dout), ptr(f), ld(f), ptr(cs), ptr(rs), rps, ptr(df), ld(df),
+                               ptr(dls), ptr(ws), _pref(ps)], ws))
+    check(lib.dfm_residual_bwd2(dtype_code(dout1), *prob[0][2], *prob[1][2], stream()), "dfm_residual_bwd2")
+    if ACCOUNT is not None:
+        _acct(0, sum(d.shape[0] * d.shape[1] * _es(d) * 3 for d in (dout1, dout2)))
+    return prob[0][0], prob[1][0]
+
+
 def residual_bwd(dout, f, colscale, rowscale=None, rows_per_scale=1, df=None):
     """Block residual x + rowscale*ls*f backward: returns (df = dout*ls*rowscale, dls = sum dout*f*rowscale)."""
     rows, C = dout.shape
@@ -498,6 +536,21 @@ def dwconv_bwd_data(dy, shape, w, k, add_identity=False, dx=None, accumulate=Fal
                                   ptr(dx), ld(dx), int(accumulate), stream()), "dfm_dwconv_bwd_data")
     if ACCOUNT is not None:
         _acct(2 * k * k * C * dy.shape[0], dy.shape[0] * C * _es(dy) * (2 + bool(accumulate)))
+    return dx
+
+
+def dwconv_bwd_data_mul(dy, shape, w, k, mul, prior=None, add_identity=False, dx=None):
+    """dx = round(round(conv(dy, flipped w) (+ dy) (+ prior)) * mul): dwconv_bwd_data (accumulating onto prior) and
+    scale_mul(mul=...) in one launch, bit-identical to the pair (the inner rounding is the pair's store)."""
+    B, H, W = shape
+    C = dy.shape[1]
+    if dx is None:
+        dx = torch.empty(dy.shape[0], C, device=dy.device, dtype=dy.dtype)
+    check(lib.dfm_dwconv_bwd_data_mul(dtype_code(dy), B, H, W, C, k, ptr(dy), ld(dy), ptr(w), int(add_identity),
+                                      ptr(prior), ld(prior) if prior is not None else 0, ptr(mul), ld(mul), ptr(dx),
+                                      ld(dx), stream()), "dfm_dwconv_bwd_data_mul")
+    if ACCOUNT is not None:
+        _acct(2 * k * k * C * dy.shape[0], dy.shape[0] * C * _es(dy) * (3 + (prior is not None)))
     return dx
 
 
@@ -686,6 +739,17 @@ def pool7(x, shape, out=None):
     if ACCOUNT is not None:
         _acct(0, (B * H * W + B * 49) * C * _es(x))
     return out
+
+
+def pool7_pair(x1, x2, shape, out1, out2):
+    """pool7(x1) into out1 and pool7(x2) into out2 (two column blocks of one buffer) in one launch."""
+    B, H, W = shape
+    check(lib.dfm_adaptive_pool7_fwd2(dtype_code(x1), B, H, W, x1.shape[1], ptr(x1), ld(x1), ptr(out1), ld(out1),
+                                      x2.shape[1], ptr(x2), ld(x2), ptr(out2), ld(out2), stream()),
+          "dfm_adaptive_pool7_fwd2")
+    if ACCOUNT is not None:
+        _acct(0, (B * H * W + B * 49) * (x1.shape[1] + x2.shape[1]) * _es(x1))
+    return out1, out2
 
 
 def pool7_bwd(dy, shape, dx=None, accumulate=False):

@@ -165,6 +165,17 @@ int dfm_layernorm_bwd(int dtype, long rows, int C, const void* x, long ldx, cons
                       const float* gamma, const float* mean, const float* rstd, const void* dres, long lddres,
                       void* dx, long lddx, int accumulate, float* dgamma, float* dbeta, void* workspace,
                       DfmPartialSum* defer, dfm_stream_t stream);
+/* dfm_layernorm_bwd of  dy + AdaptiveAvgPool2d(7)-backward(pooled)  (rows = B * H * W pixels; pooled
+ * [B * 49][ldpooled], C columns): the sum is rounded to dtype as dfm_adaptive_pool7_bwd(accumulate 1) stores
+ * it, so dx, dgamma, dbeta are bit-identical to that call onto dy followed by dfm_layernorm_bwd. On the
+ * vector path the gather runs inside the LayerNorm kernel's dy load and dy is left as it was; elsewhere
+ * the entry point issues those two launches itself and dy receives the sum. dx must not be dy.
+ * New symbol only: dfm_abi_version() stays 13. */
+int dfm_layernorm_bwd_pool(int dtype, long rows, int C, const void* x, long ldx, void* dy, long lddy,
+                           const float* gamma, const float* mean, const float* rstd, const void* dres, long lddres,
+                           void* dx, long lddx, int accumulate, float* dgamma, float* dbeta, void* workspace,
+                           DfmPartialSum* defer, const void* pooled, long ldpooled, int B, int H, int W,
+                           dfm_stream_t stream);
 
 /* ---------------------------------------------------------------- residual / layer-scale backward
  * Block.forward's x + DropPath(ls * f) (DFormer.py:173-179), backward in one pass over dout and f:
@@ -175,6 +186,15 @@ size_t dfm_residual_bwd_workspace(long rows, int C);
 int dfm_residual_bwd(int dtype, long rows, int C, const void* dout, long lddout, const void* f, long ldf,
                      const float* colscale, const float* rowscale, long rows_per_scale, void* df, long lddf,
                      float* dscale, void* workspace, DfmPartialSum* defer, dfm_stream_t stream);
+/* Two independent problems (dfm_residual_bwd's arguments each, with a workspace each) in ONE launch: the
+ * first problem's blocks, then the second's; every result bit-identical to two dfm_residual_bwd calls (the
+ * attention backward's proj / proj_e pair). New symbol only: dfm_abi_version() stays 13. */
+int dfm_residual_bwd2(int dtype, long rows1, int C1, const void* dout1, long lddout1, const void* f1, long ldf1,
+                      const float* colscale1, const float* rowscale1, long rows_per_scale1, void* df1, long lddf1,
+                      float* dscale1, void* workspace1, DfmPartialSum* defer1, long rows2, int C2, const void* dout2,
+                      long lddout2, const void* f2, long ldf2, const float* colscale2, const float* rowscale2,
+                      long rows_per_scale2, void* df2, long lddf2, float* dscale2, void* workspace2,
+                      DfmPartialSum* defer2, dfm_stream_t stream);
 
 /* ---------------------------------------------------------------- depthwise conv k x k, NHWC
  * DFormer.py:80-81 (7x7 conv/e_conv, pad 3) and DFormer.py:54,62 (3x3 pos + identity).
@@ -190,6 +210,15 @@ int dfm_dwconv_fwd(int dtype, int B, int H, int W, int C, int k, const void* x, 
 int dfm_dwconv_bwd_data(int dtype, int B, int H, int W, int C, int k, const void* dy, long lddy,
                         const float* w, int add_identity, void* dx, long lddx, int accumulate,
                         dfm_stream_t stream);
+/* bwd_data with the following elementwise scale folded into its store (the attention backward's GELU' scale
+ * of the 7x7 input gradient):  dx = round(round(conv(dy, flipped w) (+ dy) (+ prior)) * mul), the inner
+ * rounding to dtype where dfm_dwconv_bwd_data would store, so dx is bit-identical to dfm_dwconv_bwd_data
+ * (onto a dx holding prior, accumulate 1) followed by dfm_scale_mul(mul). prior (optional) may be dx; mul
+ * is required; k = 3 with add_identity only on planes the tiled kernel serves (H*W > 65536).
+ * New symbol only: dfm_abi_version() stays 13. */
+int dfm_dwconv_bwd_data_mul(int dtype, int B, int H, int W, int C, int k, const void* dy, long lddy,
+                            const float* w, int add_identity, const void* prior, long ldprior, const void* mul,
+                            long ldmul, void* dx, long lddx, dfm_stream_t stream);
 size_t dfm_dwconv_bwd_weight_workspace(int B, int H, int W, int C, int k);
 int dfm_dwconv_bwd_weight(int dtype, int B, int H, int W, int C, int k, const void* x, long ldx,
                           const void* dy, long lddy, float* dw, float* db, void* workspace,
@@ -353,6 +382,10 @@ int dfm_adaptive_pool7_fwd(int dtype, int B, int H, int W, int C, const void* x,
                            long ldy, dfm_stream_t stream);
 int dfm_adaptive_pool7_bwd(int dtype, int B, int H, int W, int C, const void* dy, long lddy, void* dx,
                            long lddx, int accumulate, dfm_stream_t stream);
+/* Two pools over the same B, H, W (LN x into C1 columns, LN x_e into C2) in ONE launch; each result
+ * bit-identical to dfm_adaptive_pool7_fwd's. New symbol only: dfm_abi_version() stays 13. */
+int dfm_adaptive_pool7_fwd2(int dtype, int B, int H, int W, int C1, const void* x1, long ldx1, void* y1, long ldy1,
+                            int C2, const void* x2, long ldx2, void* y2, long ldy2, dfm_stream_t stream);
 /* F.interpolate(bilinear, align_corners=False) NHWC [B,Hi,Wi,C] -> [B,Ho,Wo,C]
  * (DFormer.py:131, ham_head.py:226-231, MLPDecoder.py:67-73, builder.py:203). */
 int dfm_bilinear_fwd(int dtype, int B, int Hi, int Wi, int Ho, int Wo, int C, const void* x, long ldx,
