@@ -122,24 +122,6 @@ template <int G> DFM_INLINE float group_sum(float v) {
   return v;
 }
 
-// GradScaler.update (torch/amp/grad_scaler.py _amp_update_scale_) on the loss scaler's device state
-// amp = {scale, growth_tracker, applied_steps, skipped}; clears the overflow flag. One lane calls it.
-DFM_INLINE void loss_scale_step(float* amp, int* flag, float growth, float backoff, int interval) {
-  if (flag[0]) {
-    amp[0] *= backoff;
-    amp[1] = 0.f;
-    amp[3] += 1.f;
-  } else {
-    amp[2] += 1.f;
-    amp[1] += 1.f;
-    if (amp[1] >= (float)interval) {
-      amp[0] *= growth;
-      amp[1] = 0.f;
-    }
-  }
-  flag[0] = 0;
-}
-
 // 8 consecutive T elements <-> floats
 template <typename T> DFM_INLINE void ld8(const T* p, float* v);
 template <> DFM_INLINE void ld8<bf16_t>(const bf16_t* p, float* v) {
@@ -291,6 +273,11 @@ static inline int dfm_dtype_size(int dtype) { return dtype == DFM_F32 ? 4 : 2; }
   } while (0)
 #define DFM_CHECK_DTYPE(dtype) DFM_DTYPE_SWITCH(dtype, DfmT_, (void)0)
 #define DFM_CHECK_DTYPE16(dtype) DFM_DTYPE_SWITCH16(dtype, DfmT_, (void)0)
+// The optional 16-bit shadow copy of a float32 kernel's result: copy_dtype must be 16-bit, except that callers
+// without a copy may pass DFM_F32 (either instantiation then computes the same float32 results).
+static inline int copy_code(const void* copy, int copy_dtype) {
+  return !copy && copy_dtype == DFM_F32 ? DFM_BF16 : copy_dtype;
+}
 
 // ---- second stage of the deterministic two-stage column reductions:
 // out[e] (+)= sum_{b < nblk} part[b * n + e], fixed summation order; 64 columns x 16 row-lanes

@@ -1,5 +1,5 @@
 // Bandwidth-bound helpers: column reductions (bias / layer-scale grads, BatchNorm statistics),
-// activation backward, residual chain rule, dtype casts, NMF multiplicative updates and AdamW.
+// activation backward, residual chain rule, dtype casts and NMF multiplicative updates.
 // All reductions are two-stage with fixed order (deterministic, no float atomics).
 #include <cstdlib>
 
@@ -478,57 +478,6 @@ __global__ void softmax_rows_bwd_kernel(long rows, int R, const float* __restric
   }
 }
 
-// ---- AdamW (torch.optim.AdamW semantics, decoupled weight decay)
-template <typename TC>
-__global__ void adamw_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, float lr, float b1, float b2, float eps, float wd, float bc1,
-                             float bc2_sqrt, float gscale, TC* __restrict__ copy) {
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
-    p[i] = pi;
-    if (copy) copy[i] = Num<TC>::from_f(pi);
-  }
-}
-// Same update with lr and step read from device memory (hyper = [lr, step]), so a captured HIP
-// graph replays every optimizer step without host-baked scalars. With the fp16 loss scaler's device
-// state amp = {scale, growth_tracker, applied_steps, skipped} and overflow flag: the step is skipped
-// when flag[0] is set (GradScaler.step), gradients are unscaled by 1/scale and the step count is
-// amp[2] + 1 (torch's AdamW counts applied steps only).
-template <typename TC>
-__global__ void adamw_dev_kernel(long n, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                 float* __restrict__ v, const float* __restrict__ hyper, float b1, float b2,
-                                 float eps, float wd, float gscale, TC* __restrict__ copy,
-                                 const float* __restrict__ amp, const int* __restrict__ flag) {
-  if (flag && flag[0]) return;
-  const float lr = hyper[0], step = amp ? amp[2] + 1.f : hyper[1];
-  if (amp) gscale /= amp[0];
-  const float bc1 = 1.f - powf(b1, step), bc2_sqrt = sqrtf(1.f - powf(b2, step));
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gscale;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi;
-    v[i] = vi;
-    pi -= (lr / bc1) * mi / (sqrtf(vi) / bc2_sqrt + eps);
-    p[i] = pi;
-    if (copy) copy[i] = Num<TC>::from_f(pi);
-  }
-}
-// GradScaler.update (torch/amp/grad_scaler.py _amp_update_scale_) on the device state, after the
-// step's AdamW launches have read it; clears the overflow flag for the next step. One lane.
-__global__ void loss_scale_update_kernel(float* __restrict__ amp, int* __restrict__ flag, float growth,
-                                         float backoff, int interval) {
-  if (threadIdx.x != 0) return;
-  loss_scale_step(amp, flag, growth, backoff, interval);
-}
-
 // o1 = src * m1, o2 = src * m2 (the two products of one gradient against the two factors of
 // an elementwise product, DFormer.py:134-135: d(q*a) -> dq = d*a, da = d*q): one read of src.
 template <typename T>
@@ -552,14 +501,6 @@ __global__ void dual_mul_vec_kernel(long rows, int C, const T* __restrict__ src,
     st8<T>(o1 + r * ldo1 + c, a);
     st8<T>(o2 + r * ldo2 + c, b);
   }
-}
-
-// flag[0] = 1 if any element of g is inf / nan (the GradScaler's found_inf, torch/amp/grad_scaler.py)
-__global__ void nonfinite_kernel(long n, const float* __restrict__ g, int* __restrict__ flag) {
-  bool bad = false;
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    bad |= !isfinite(g[i]);
-  if (__any(bad) && (threadIdx.x & 63) == 0) flag[0] = 1;
 }
 }  // namespace
 
@@ -898,10 +839,6 @@ extern "C" int dfm_bn_bwd_apply(int dtype, long rows, int C, const void* x, long
   return DFM_OK;
 }
 
-// The optional 16-bit shadow copy of a float32 kernel's result: copy_dtype must be 16-bit, except that callers
-// without a copy may pass DFM_F32 (either instantiation then computes the same float32 results).
-static int copy_code(const void* copy, int copy_dtype) { return !copy && copy_dtype == DFM_F32 ? DFM_BF16 : copy_dtype; }
-
 extern "C" int dfm_nmf_update(long n, const float* a, const float* num, const float* den, float eps, float* out,
                               void* out16, int copy_dtype, dfm_stream_t stream) {
   DFM_DTYPE_SWITCH16(copy_code(out16, copy_dtype), TC,
@@ -1102,14 +1039,6 @@ extern "C" int dfm_nmf_update_bwd_mm(int batch, long rows, int R, const float* g
   return DFM_OK;
 }
 
-extern "C" int dfm_grad_nonfinite(long n, const float* g, int* flag, dfm_stream_t stream) {
-  DFM_CHECK_ARG(g && flag && n >= 0, "dfm_grad_nonfinite: bad argument");
-  if (n == 0) return DFM_OK;
-  DFM_LAUNCH(nonfinite_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, g, flag);
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
 extern "C" int dfm_softmax_rows(long rows, int R, const float* x, float* y, dfm_stream_t stream) {
   DFM_LAUNCH(softmax_rows_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, rows, R, x, y);
   DFM_LAUNCH_CHECK();
@@ -1120,56 +1049,6 @@ extern "C" int dfm_softmax_rows_bwd(long rows, int R, const float* y, const floa
                                     dfm_stream_t stream) {
   DFM_LAUNCH(softmax_rows_bwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, rows, R, y, dy, dx,
                      acc);
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
-extern "C" int dfm_adamw(long n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2,
-                         float eps, float wd, int step, float gscale, void* copy, int copy_dtype,
-                         dfm_stream_t stream) {
-  DFM_CHECK_DTYPE16(copy_code(copy, copy_dtype));
-  DFM_CHECK_ARG(p && g && m && v && step >= 1, "dfm_adamw: bad argument");
-  if (n == 0) return DFM_OK;
-  const float bc1 = 1.f - powf(beta1, (float)step);
-  const float bc2 = 1.f - powf(beta2, (float)step);
-  DFM_DTYPE_SWITCH16(copy_code(copy, copy_dtype), TC,
-                     DFM_LAUNCH(adamw_kernel<TC>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v, lr,
-                                beta1, beta2, eps, wd, bc1, sqrtf(bc2), gscale, (TC*)copy));
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
-extern "C" int dfm_adamw_dev(long n, float* p, const float* g, float* m, float* v, const float* hyper, float beta1,
-                             float beta2, float eps, float wd, float gscale, void* copy, int copy_dtype,
-                             dfm_stream_t stream) {
-  DFM_CHECK_DTYPE16(copy_code(copy, copy_dtype));
-  DFM_CHECK_ARG(p && g && m && v && hyper, "dfm_adamw_dev: bad argument");
-  if (n == 0) return DFM_OK;
-  DFM_DTYPE_SWITCH16(copy_code(copy, copy_dtype), TC,
-                     DFM_LAUNCH(adamw_dev_kernel<TC>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v,
-                                hyper, beta1, beta2, eps, wd, gscale, (TC*)copy, nullptr, nullptr));
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
-extern "C" int dfm_adamw_amp(long n, float* p, const float* g, float* m, float* v, const float* hyper,
-                             const float* amp, const int* flag, float beta1, float beta2, float eps, float wd,
-                             float gscale, void* copy, int copy_dtype, dfm_stream_t stream) {
-  DFM_CHECK_DTYPE16(copy_code(copy, copy_dtype));
-  DFM_CHECK_ARG(p && g && m && v && hyper && amp && flag, "dfm_adamw_amp: bad argument");
-  if (n == 0) return DFM_OK;
-  DFM_DTYPE_SWITCH16(copy_code(copy, copy_dtype), TC,
-                     DFM_LAUNCH(adamw_dev_kernel<TC>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v,
-                                hyper, beta1, beta2, eps, wd, gscale, (TC*)copy, amp, flag));
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
-}
-
-extern "C" int dfm_loss_scale_update(float* amp, int* flag, float growth, float backoff, int interval,
-                                     dfm_stream_t stream) {
-  DFM_CHECK_ARG(amp && flag && interval > 0, "dfm_loss_scale_update: bad argument");
-  DFM_LAUNCH(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, amp, flag, growth, backoff,
-             interval);
   DFM_LAUNCH_CHECK();
   return DFM_OK;
 }

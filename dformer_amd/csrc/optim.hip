@@ -1,5 +1,6 @@
-// Optimizer options of FusedAdamW over the flat float32 group buffers: gradient accumulation,
-// clipping by the global gradient norm, and an exponential moving average of the weights.
+// The optimizer tail of a training step over the flat float32 group buffers: the AdamW update, the
+// fp16 loss scaler, and FusedAdamW's options (gradient accumulation, clipping by the global gradient
+// norm, an exponential moving average of the weights).
 // Every decision a step takes (is this the window's last micro-step, did the fp16 gradients
 // overflow, how much to clip) is read from device memory, so one captured HIP graph serves every
 // micro-step. Reductions are two-stage with a fixed order: no float atomics, bit-reproducible.
@@ -81,39 +82,50 @@ __global__ __launch_bounds__(256) void grad_clip_coef_kernel(int npart, const fl
   clip[1] = c > 1.f ? 1.f : c;  // NaN stays NaN (torch.clamp)
 }
 
-// adamw_dev_kernel (elementwise.hip) with the options, each a pointer that may be NULL:
+// AdamW (torch.optim.AdamW semantics, decoupled weight decay) over a flat float32 buffer: the one
+// update of every dfm_adamw* entry point. lr and the bias corrections come by value (hyper NULL,
+// dfm_adamw) or from device memory, hyper = {lr, step}, so a captured HIP graph replays every step
+// without host-baked scalars. With the fp16 loss scaler's device state amp = {scale, growth_tracker,
+// applied_steps, skipped} and overflow flag: the step is skipped when flag[0] is set
+// (GradScaler.step), gradients are unscaled by 1/scale and the step count is amp[2] + 1 (torch's
+// AdamW counts applied steps only).
+// OPT = false is that and nothing else: no option is read and g is never written. OPT = true adds
+// the options, each a pointer that may be NULL:
 //   win    nothing is written unless this is the window's last micro-step
-//   flag   on overflow the update is skipped, a consumed gradient buffer still cleared
 //   clip   the gradient is multiplied by clip[1] (grad_clip_coef_kernel)
 //   ema    ema = d * ema + (1 - d) * p_new in the same pass
-//   clear_g  g is the accumulation buffer: zero is written back once it is consumed
-// With all of them off the arithmetic is adamw_dev_kernel's, bit for bit.
-template <typename TC>
-__global__ void adamw_opt_kernel(long n, float* __restrict__ p, float* __restrict__ g, int clear_g,
-                                 float* __restrict__ m, float* __restrict__ v, const float* __restrict__ hyper,
-                                 float b1, float b2, float eps, float wd, float gscale, TC* __restrict__ copy,
-                                 const float* __restrict__ amp, const int* __restrict__ flag,
-                                 const float* __restrict__ clip, const int* __restrict__ win,
-                                 float* __restrict__ ema, float d) {
-  if (window_open(win)) return;
+//   clear_g  g is the accumulation buffer: zero is written back once it is consumed, also by a
+//            step that flag skips
+// Every rounding is spelled out, so the bits are the source's and not a contraction the compiler
+// picks per instantiation (which product of a sum goes into the fma):
+//   m = fma(1 - b1, g, rn(b1 m))   v = fma(g, rn((1 - b2) g), rn(b2 v))   p = fma(1 - lr wd, p, -q)
+//   q = rn(step_size m) / (sqrt(v) / bc2_sqrt + eps)
+template <typename TC, bool OPT>
+__global__ void adamw_kernel(long n, float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                             float* __restrict__ v, const float* __restrict__ hyper, float lr, float bc1,
+                             float bc2_sqrt, float b1, float b2, float eps, float wd, float gscale,
+                             TC* __restrict__ copy, const float* __restrict__ amp, const int* __restrict__ flag,
+                             const float* __restrict__ clip, const int* __restrict__ win, float* __restrict__ ema,
+                             float d, int clear_g) {
+  if (OPT && window_open(win)) return;
   const long t = blockIdx.x * (long)blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
   if (flag && flag[0]) {
-    if (clear_g)
+    if (OPT && clear_g)
       for (long i = t; i < n; i += stride) g[i] = 0.f;
     return;
   }
-  const float lr = hyper[0], step = amp ? amp[2] + 1.f : hyper[1];
+  if (hyper) {
+    const float step = amp ? amp[2] + 1.f : hyper[1];
+    lr = hyper[0];
+    bc1 = 1.f - powf(b1, step);
+    bc2_sqrt = sqrtf(1.f - powf(b2, step));
+  }
   if (amp) gscale /= amp[0];
-  const float coef = clip ? clip[1] : 1.f;
-  const float bc1 = 1.f - powf(b1, step), bc2_sqrt = sqrtf(1.f - powf(b2, step));
-  // adamw_dev_kernel's expressions with every rounding spelled out, in the form the compiler
-  // contracts them to there (which product of a sum goes into the fma is its choice per kernel,
-  // and the two kernels have to agree bit for bit):
-  //   m = fma(1 - b1, g, rn(b1 m))   v = fma(g, rn((1 - b2) g), rn(b2 v))   p = fma(1 - lr wd, p, -q)
+  const float coef = OPT && clip ? clip[1] : 1.f;
   const float decay = __fmaf_rn(-lr, wd, 1.f), step_size = lr / bc1, omb1 = 1.f - b1, omb2 = 1.f - b2, omd = 1.f - d;
   for (long i = t; i < n; i += stride) {
     float gi = __fmul_rn(g[i], gscale);
-    if (clip) gi = __fmul_rn(gi, coef);
+    if (OPT && clip) gi = __fmul_rn(gi, coef);
     const float mi = __fmaf_rn(omb1, gi, __fmul_rn(b1, m[i]));
     const float vi = __fmaf_rn(gi, __fmul_rn(omb2, gi), __fmul_rn(b2, v[i]));
     m[i] = mi;
@@ -122,20 +134,55 @@ __global__ void adamw_opt_kernel(long n, float* __restrict__ p, float* __restric
     const float pi = __fmaf_rn(decay, p[i], -q);
     p[i] = pi;
     if (copy) copy[i] = Num<TC>::from_f(pi);
-    if (ema) ema[i] = __fmaf_rn(d, ema[i], __fmul_rn(omd, pi));
-    if (clear_g) g[i] = 0.f;
+    if (OPT && ema) ema[i] = __fmaf_rn(d, ema[i], __fmul_rn(omd, pi));
+    if (OPT && clear_g) g[i] = 0.f;
   }
 }
 
-// loss_scale_update_kernel that leaves the scaler alone inside an accumulation window
-__global__ void loss_scale_update_win_kernel(float* __restrict__ amp, int* __restrict__ flag, float growth,
-                                             float backoff, int interval, const int* __restrict__ win) {
+// GradScaler.update (torch/amp/grad_scaler.py _amp_update_scale_) on the loss scaler's device state,
+// after the step's AdamW launches have read it; clears the overflow flag for the next step. One
+// lane. Inside an accumulation window (win, NULL = no window) the scaler is left alone.
+__global__ void loss_scale_update_kernel(float* __restrict__ amp, int* __restrict__ flag, float growth,
+                                         float backoff, int interval, const int* __restrict__ win) {
   if (threadIdx.x != 0 || window_open(win)) return;
-  loss_scale_step(amp, flag, growth, backoff, interval);
+  if (flag[0]) {
+    amp[0] *= backoff;
+    amp[1] = 0.f;
+    amp[3] += 1.f;
+  } else {
+    amp[2] += 1.f;
+    amp[1] += 1.f;
+    if (amp[1] >= (float)interval) {
+      amp[0] *= growth;
+      amp[1] = 0.f;
+    }
+  }
+  flag[0] = 0;
 }
 
-// no shadow copy: the caller passes copy_dtype 0 (as for dfm_adamw_dev); any 16-bit instantiation serves
-int copy_code(const void* copy, int copy_dtype) { return !copy && copy_dtype == DFM_F32 ? DFM_BF16 : copy_dtype; }
+// flag[0] = 1 if any element of g is inf / nan (the GradScaler's found_inf, torch/amp/grad_scaler.py)
+__global__ void nonfinite_kernel(long n, const float* __restrict__ g, int* __restrict__ flag) {
+  bool bad = false;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    bad |= !isfinite(g[i]);
+  if (__any(bad) && (threadIdx.x & 63) == 0) flag[0] = 1;
+}
+
+// The one AdamW launch, after the entry point's argument checks: OPT = true as soon as one option is on
+int adamw_launch(long n, float* p, float* g, float* m, float* v, const float* hyper, float lr, float bc1,
+                 float bc2_sqrt, float b1, float b2, float eps, float wd, float gscale, void* copy, int copy_dtype,
+                 const float* amp, const int* flag, const float* clip, const int* win, float* ema, float d,
+                 int clear_g, dfm_stream_t stream) {
+  if (n == 0) return DFM_OK;
+  const bool opt = win || clip || ema || clear_g;
+  DFM_DTYPE_SWITCH16(copy_code(copy, copy_dtype), TC, {
+    const auto kern = opt ? adamw_kernel<TC, true> : adamw_kernel<TC, false>;
+    DFM_LAUNCH(kern, dim3(opt_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g, m, v, hyper, lr, bc1, bc2_sqrt, b1,
+               b2, eps, wd, gscale, (TC*)copy, amp, flag, clip, win, ema, d, clear_g);
+  });
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
 }  // namespace
 
 extern "C" int dfm_grad_accumulate(long n, float* acc, const float* g, dfm_stream_t stream) {
@@ -166,6 +213,43 @@ extern "C" int dfm_grad_clip_coef(int npart, const float* part, float grad_scale
   return DFM_OK;
 }
 
+extern "C" int dfm_grad_nonfinite(long n, const float* g, int* flag, dfm_stream_t stream) {
+  DFM_CHECK_ARG(g && flag && n >= 0, "dfm_grad_nonfinite: bad argument");
+  if (n == 0) return DFM_OK;
+  DFM_LAUNCH(nonfinite_kernel, dim3(opt_grid(n)), dim3(256), 0, (hipStream_t)stream, n, g, flag);
+  DFM_LAUNCH_CHECK();
+  return DFM_OK;
+}
+
+extern "C" int dfm_adamw(long n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2,
+                         float eps, float wd, int step, float gscale, void* copy, int copy_dtype,
+                         dfm_stream_t stream) {
+  DFM_CHECK_DTYPE16(copy_code(copy, copy_dtype));
+  DFM_CHECK_ARG(p && g && m && v && step >= 1, "dfm_adamw: bad argument");
+  const float bc1 = 1.f - powf(beta1, (float)step);
+  const float bc2 = 1.f - powf(beta2, (float)step);
+  return adamw_launch(n, p, const_cast<float*>(g), m, v, nullptr, lr, bc1, sqrtf(bc2), beta1, beta2, eps, wd, gscale,
+                      copy, copy_dtype, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0, stream);
+}
+
+extern "C" int dfm_adamw_dev(long n, float* p, const float* g, float* m, float* v, const float* hyper, float beta1,
+                             float beta2, float eps, float wd, float gscale, void* copy, int copy_dtype,
+                             dfm_stream_t stream) {
+  DFM_CHECK_DTYPE16(copy_code(copy, copy_dtype));
+  DFM_CHECK_ARG(p && g && m && v && hyper, "dfm_adamw_dev: bad argument");
+  return adamw_launch(n, p, const_cast<float*>(g), m, v, hyper, 0.f, 0.f, 0.f, beta1, beta2, eps, wd, gscale, copy,
+                      copy_dtype, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0, stream);
+}
+
+extern "C" int dfm_adamw_amp(long n, float* p, const float* g, float* m, float* v, const float* hyper,
+                             const float* amp, const int* flag, float beta1, float beta2, float eps, float wd,
+                             float gscale, void* copy, int copy_dtype, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE16(copy_code(copy, copy_dtype));
+  DFM_CHECK_ARG(p && g && m && v && hyper && amp && flag, "dfm_adamw_amp: bad argument");
+  return adamw_launch(n, p, const_cast<float*>(g), m, v, hyper, 0.f, 0.f, 0.f, beta1, beta2, eps, wd, gscale, copy,
+                      copy_dtype, amp, flag, nullptr, nullptr, nullptr, 0.f, 0, stream);
+}
+
 extern "C" int dfm_adamw_opt(long n, float* p, float* g, int clear_g, float* m, float* v, const float* hyper,
                              const float* amp, const int* flag, const float* clip_state, const int* win, float* ema,
                              float ema_decay, float beta1, float beta2, float eps, float wd, float gscale,
@@ -174,20 +258,21 @@ extern "C" int dfm_adamw_opt(long n, float* p, float* g, int clear_g, float* m, 
   DFM_CHECK_ARG(p && g && m && v && hyper && !amp == !flag, "dfm_adamw_opt: bad argument");
   DFM_CHECK_ARG(!ema || (ema_decay >= 0.f && ema_decay < 1.f), "dfm_adamw_opt: ema_decay %g outside [0, 1)",
                 (double)ema_decay);
-  if (n == 0) return DFM_OK;
-  DFM_DTYPE_SWITCH16(copy_code(copy, copy_dtype), TC,
-                     DFM_LAUNCH(adamw_opt_kernel<TC>, dim3(opt_grid(n)), dim3(256), 0, (hipStream_t)stream, n, p, g,
-                                clear_g, m, v, hyper, beta1, beta2, eps, wd, gscale, (TC*)copy, amp, flag, clip_state,
-                                win, ema, ema_decay));
-  DFM_LAUNCH_CHECK();
-  return DFM_OK;
+  return adamw_launch(n, p, g, m, v, hyper, 0.f, 0.f, 0.f, beta1, beta2, eps, wd, gscale, copy, copy_dtype, amp, flag,
+                      clip_state, win, ema, ema_decay, clear_g, stream);
 }
 
 extern "C" int dfm_loss_scale_update_win(float* amp, int* flag, float growth, float backoff, int interval,
                                          const int* win, dfm_stream_t stream) {
   DFM_CHECK_ARG(amp && flag && interval > 0, "dfm_loss_scale_update_win: bad argument");
-  DFM_LAUNCH(loss_scale_update_win_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, amp, flag, growth, backoff,
+  DFM_LAUNCH(loss_scale_update_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, amp, flag, growth, backoff,
              interval, win);
   DFM_LAUNCH_CHECK();
   return DFM_OK;
+}
+
+extern "C" int dfm_loss_scale_update(float* amp, int* flag, float growth, float backoff, int interval,
+                                     dfm_stream_t stream) {
+  DFM_CHECK_ARG(amp && flag && interval > 0, "dfm_loss_scale_update: bad argument");
+  return dfm_loss_scale_update_win(amp, flag, growth, backoff, interval, nullptr, stream);
 }

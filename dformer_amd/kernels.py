@@ -1607,38 +1607,7 @@ def fss_fuse(low, B, h, w, prob, hs, ws, out_hw, alpha):
     return out
 
 
-# -------------------------------------------------------------------------------------- AdamW
-def loss_scale_update(amp, flag, growth, backoff, interval):
-    check(lib.dfm_loss_scale_update(ptr(amp), ptr(flag), growth, backoff, interval, stream()),
-          "dfm_loss_scale_update")
-
-
-def grad_nonfinite(g, flag):
-    """flag (int32 [1], zeroed by the caller) := 1 if any element of g is inf / nan."""
-    check(lib.dfm_grad_nonfinite(g.numel(), ptr(g), ptr(flag), stream()), "dfm_grad_nonfinite")
-    return flag
-
-
-def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, bf16_copy=None, hyper=None,
-          amp=None, flag=None):
-    """AdamW step; with `hyper` (device float32 [lr, step]) lr and step are read on the device
-    (lr / step arguments ignored) so the launch can live in a replayed HIP graph. With the loss
-    scaler's device state `amp` and overflow `flag` the step is skipped / unscaled on the device."""
-    cdt = dtype_code(bf16_copy) if bf16_copy is not None else 0
-    if amp is not None:
-        check(lib.dfm_adamw_amp(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), ptr(hyper), ptr(amp), ptr(flag), beta1,
-                                beta2, eps, weight_decay, grad_scale, ptr(bf16_copy), cdt, stream()), "dfm_adamw_amp")
-    elif hyper is not None:
-        check(lib.dfm_adamw_dev(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), ptr(hyper), beta1, beta2, eps,
-                                weight_decay, grad_scale, ptr(bf16_copy), cdt, stream()), "dfm_adamw_dev")
-    else:
-        check(lib.dfm_adamw(p.numel(), ptr(p), ptr(g), ptr(m), ptr(v), lr, beta1, beta2, eps, weight_decay, step,
-                            grad_scale, ptr(bf16_copy), cdt, stream()), "dfm_adamw")
-    if ACCOUNT is not None:
-        _acct(0, p.numel() * (28 + (2 if bf16_copy is not None else 0)))
-
-
-# ------------------------------------------------------------------------- optimizer options
+# -------------------------------------------------------------------------------------- optimizer
 def _f32_flat(t, what):
     if t.dtype != torch.float32 or not t.is_contiguous():
         raise TypeError(f"dformer_amd: {what} must be a contiguous float32 buffer")
@@ -1650,6 +1619,47 @@ def _win(win):
     if win is not None and (win.dtype != torch.int32 or win.numel() < 2):
         raise ValueError("dformer_amd: win is int32 [2]")
     return ptr(win)
+
+
+def loss_scale_update(amp, flag, growth, backoff, interval, win=None):
+    """GradScaler.update on the device state; inside an accumulation window (`win`) the scaler is left alone."""
+    check(lib.dfm_loss_scale_update_win(ptr(amp), ptr(flag), growth, backoff, interval, _win(win), stream()),
+          "dfm_loss_scale_update_win")
+
+
+def grad_nonfinite(g, flag):
+    """flag (int32 [1], zeroed by the caller) := 1 if any element of g is inf / nan."""
+    check(lib.dfm_grad_nonfinite(g.numel(), ptr(g), ptr(flag), stream()), "dfm_grad_nonfinite")
+    return flag
+
+
+def adamw(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, bf16_copy=None, hyper=None,
+          amp=None, flag=None, clip_state=None, win=None, ema=None, ema_decay=0.0, clear_g=False):
+    """AdamW step; with `hyper` (device float32 [lr, step]) lr and step are read on the device
+    (lr / step arguments ignored) so the launch can live in a replayed HIP graph. With the loss
+    scaler's device state `amp` and overflow `flag` the step is skipped / unscaled on the device.
+    The options need `hyper` and are off when None: the gradient times clip_state[1]; no write
+    unless `win` (int32 {micro_index, accum_steps}) is on its last micro-step; `ema` updated in the
+    same pass; clear_g zeroes g (the accumulation buffer)."""
+    n = p.numel()
+    for t, what in ((g, "g"), (m, "m"), (v, "v"), (ema, "ema"), (bf16_copy, "bf16_copy")):
+        if t is not None and t.numel() != n:
+            raise ValueError(f"adamw: {what} has {t.numel()} elements, p has {n}")
+    cdt = dtype_code(bf16_copy) if bf16_copy is not None else 0
+    bufs = [ptr(_f32_flat(t, what)) for t, what in ((p, "p"), (g, "g"), (m, "m"), (v, "v"))]
+    if hyper is not None:
+        check(lib.dfm_adamw_opt(n, bufs[0], bufs[1], int(clear_g), bufs[2], bufs[3], ptr(hyper), ptr(amp), ptr(flag),
+                                ptr(clip_state), _win(win), ptr(None if ema is None else _f32_flat(ema, "ema")),
+                                ema_decay, beta1, beta2, eps, weight_decay, grad_scale, ptr(bf16_copy), cdt, stream()),
+              "dfm_adamw_opt")
+    else:
+        if any(o is not None for o in (amp, flag, clip_state, win, ema)) or clear_g:
+            raise ValueError("adamw: amp / flag and the options need hyper")
+        check(lib.dfm_adamw(n, *bufs, lr, beta1, beta2, eps, weight_decay, step, grad_scale, ptr(bf16_copy), cdt,
+                            stream()), "dfm_adamw")
+    if ACCOUNT is not None:
+        _acct(0, n * (28 + (2 if bf16_copy is not None else 0) + (8 if ema is not None else 0)
+                      + (4 if clear_g else 0)))
 
 
 def grad_accumulate(acc, g):
@@ -1687,28 +1697,3 @@ def grad_clip_coef(part, grad_scale, max_norm, clip_state, amp=None, win=None):
                                  ptr(clip_state), _win(win), stream()), "dfm_grad_clip_coef")
     if ACCOUNT is not None:
         _acct(0, part.numel() * 4)
-
-
-def adamw_opt(p, g, m, v, hyper, beta1, beta2, eps, weight_decay, grad_scale=1.0, bf16_copy=None, amp=None,
-              flag=None, clip_state=None, win=None, ema=None, ema_decay=0.0, clear_g=False):
-    """adamw(hyper=...) with the optimizer options, each off when None: the gradient times
-    clip_state[1]; no write unless `win` (int32 {micro_index, accum_steps}) is on its last
-    micro-step; `ema` updated in the same pass; clear_g zeroes g (the accumulation buffer)."""
-    n = p.numel()
-    for t, what in ((g, "g"), (m, "m"), (v, "v"), (ema, "ema"), (bf16_copy, "bf16_copy")):
-        if t is not None and t.numel() != n:
-            raise ValueError(f"adamw_opt: {what} has {t.numel()} elements, p has {n}")
-    cdt = dtype_code(bf16_copy) if bf16_copy is not None else 0
-    check(lib.dfm_adamw_opt(n, ptr(_f32_flat(p, "p")), ptr(_f32_flat(g, "g")), int(clear_g), ptr(_f32_flat(m, "m")),
-                            ptr(_f32_flat(v, "v")), ptr(hyper), ptr(amp), ptr(flag), ptr(clip_state), _win(win),
-                            ptr(None if ema is None else _f32_flat(ema, "ema")), ema_decay, beta1, beta2, eps,
-                            weight_decay, grad_scale, ptr(bf16_copy), cdt, stream()), "dfm_adamw_opt")
-    if ACCOUNT is not None:
-        _acct(0, n * (28 + (2 if bf16_copy is not None else 0) + (8 if ema is not None else 0)
-                      + (4 if clear_g else 0)))
-
-
-def loss_scale_update_win(amp, flag, growth, backoff, interval, win=None):
-    """loss_scale_update that leaves the scaler alone inside an accumulation window."""
-    check(lib.dfm_loss_scale_update_win(ptr(amp), ptr(flag), growth, backoff, interval, _win(win), stream()),
-          "dfm_loss_scale_update_win")

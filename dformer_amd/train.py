@@ -304,14 +304,10 @@ class LossScaler:
         for g in grads:
             K.grad_nonfinite(g, self.found_inf)
 
-    def update_device(self):
+    def update_device(self, win=None):
+        """GradScaler.update; once per accumulation window: nothing moves unless `win` is on its last micro-step."""
         K.loss_scale_update(self.state, self.found_inf, self.growth_factor, self.backoff_factor,
-                            self.growth_interval)
-
-    def update_device_win(self, win):
-        """update_device once per accumulation window: nothing moves unless `win` is on its last micro-step."""
-        K.loss_scale_update_win(self.state, self.found_inf, self.growth_factor, self.backoff_factor,
-                                self.growth_interval, win)
+                            self.growth_interval, win)
 
     def update(self, found_inf):
         """GradScaler.update on the state from the host (what dfm_loss_scale_update does on the
@@ -420,9 +416,6 @@ class FusedAdamW:
         for p in self.ungrouped:
             p.grad = None
         gscale = 1.0 / (self.world * self.accum_steps)
-        sc = self.scaler
-        if sc is not None and not self.options:  # GradScaler.unscale_ / step / update, decided on the device
-            sc.flag_nonfinite([g.grad for g in self.groups])
         micro = self.advance()
         lr = self.lr if lr is None else lr
         if not self.external_hyper:
@@ -433,15 +426,30 @@ class FusedAdamW:
         keep = [(g, off, k, g.flat[off:off + k].clone(), g.m[off:off + k].clone(), g.v[off:off + k].clone(),
                  g.ema[off:off + k].clone() if g.ema is not None else None)
                 for g, off, k in self.buckets.unfired]
-        if self.options:
-            self._update_with_options(gscale)
-        else:
+        # accumulate -> (nonfinite, norm) -> update -> GradScaler.update, decided on the device and the
+        # same launches on every micro-step: what is not due before the window's last micro-step
+        # returns at once there (`win`). With the options off only the update (and the scaler) is left.
+        sc = self.scaler
+        amp, flag = (sc.state, sc.found_inf) if sc is not None else (None, None)
+        accum = self.accum_steps > 1
+        if accum:
             for g in self.groups:
-                K.adamw(g.flat, g.grad, g.m, g.v, lr, self.betas[0], self.betas[1], self.eps, g.wd, 1, gscale,
-                        g.shadow, hyper=self.hyper, amp=sc.state if sc is not None else None,
-                        flag=sc.found_inf if sc is not None else None)
-            if sc is not None:
-                sc.update_device()
+                K.grad_accumulate(g.acc, g.grad)
+        grads = [g.acc if accum else g.grad for g in self.groups]
+        if self.partials is not None:  # one read serves the norm and the scaler's inf / nan check
+            nb = K.sumsq_blocks()
+            for j, gr in enumerate(grads):
+                K.grad_sumsq(gr, self.partials[j * nb:(j + 1) * nb], flag=flag, win=self.win)
+            if self.max_grad_norm is not None:
+                K.grad_clip_coef(self.partials, gscale, self.max_grad_norm, self.clip_state, amp=amp, win=self.win)
+        elif sc is not None:
+            sc.flag_nonfinite(grads)
+        for g, gr in zip(self.groups, grads):
+            K.adamw(g.flat, gr, g.m, g.v, lr, self.betas[0], self.betas[1], self.eps, g.wd, 1, gscale, g.shadow,
+                    hyper=self.hyper, amp=amp, flag=flag, clip_state=self.clip_state, win=self.win, ema=g.ema,
+                    ema_decay=self.ema_decay or 0.0, clear_g=accum)
+        if sc is not None:
+            sc.update_device(self.win)
         for g, off, k, p0, m0, v0, e0 in keep:
             g.flat[off:off + k].copy_(p0)
             g.m[off:off + k].copy_(m0)
@@ -471,29 +479,6 @@ class FusedAdamW:
             self.hyper[1].fill_(float(self._steps))
         if self.win is not None:
             self.win[0].fill_(micro)
-
-    def _update_with_options(self, gscale):
-        """accumulate -> (nonfinite, norm) -> update, the same launches on every micro-step: what is
-        not due before the window's last micro-step returns at once on the device (`win`)."""
-        sc = self.scaler
-        amp, flag = (sc.state, sc.found_inf) if sc is not None else (None, None)
-        accum = self.accum_steps > 1
-        if accum:
-            for g in self.groups:
-                K.grad_accumulate(g.acc, g.grad)
-        grads = [g.acc if accum else g.grad for g in self.groups]
-        if self.partials is not None:  # one read serves the norm and the scaler's inf / nan check
-            nb = K.sumsq_blocks()
-            for j, gr in enumerate(grads):
-                K.grad_sumsq(gr, self.partials[j * nb:(j + 1) * nb], flag=flag, win=self.win)
-            if self.max_grad_norm is not None:
-                K.grad_clip_coef(self.partials, gscale, self.max_grad_norm, self.clip_state, amp=amp, win=self.win)
-        for g, gr in zip(self.groups, grads):
-            K.adamw_opt(g.flat, gr, g.m, g.v, self.hyper, self.betas[0], self.betas[1], self.eps, g.wd, gscale,
-                        g.shadow, amp=amp, flag=flag, clip_state=self.clip_state, win=self.win, ema=g.ema,
-                        ema_decay=self.ema_decay or 0.0, clear_g=accum)
-        if sc is not None:
-            sc.update_device_win(self.win)
 
     def grad_norm(self):
         """The last applied window's global gradient norm before clipping (max_grad_norm only).

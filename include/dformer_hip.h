@@ -758,10 +758,11 @@ int dfm_fss_loss_bwd(int dtype_out, int B, int h, int w, int hs, int ws, int H, 
 int dfm_fss_fuse_fwd(int dtype, int B, int h, int w, const void* low, long ldl, int hs, int ws, const float* prob,
                      int H, int W, float alpha, float* out, dfm_stream_t stream);
 
-/* ---------------------------------------------------------------- optimizer
+/* ---------------------------------------------------------------- optimizer (csrc/optim.hip)
  * torch.optim.AdamW step (train.py:210-216) over a flat float32 parameter buffer; optional
  * 16-bit shadow copy (copy_dtype DFM_BF16 / DFM_F16) for the next step's GEMM operands.
- * grad_scale multiplies g (1/world, and 1/loss-scale on the fp16 path). */
+ * grad_scale multiplies g (1/world, and 1/loss-scale on the fp16 path). The four dfm_adamw* entry
+ * points launch one kernel source with every rounding explicit: the same update, the same bits. */
 int dfm_adamw(long n, float* p, const float* g, float* m, float* v, float lr, float beta1, float beta2,
               float eps, float weight_decay, int step, float grad_scale, void* copy, int copy_dtype,
               dfm_stream_t stream);
@@ -783,7 +784,7 @@ int dfm_adamw_amp(long n, float* p, const float* g, float* m, float* v, const fl
                   void* copy, int copy_dtype, dfm_stream_t stream);
 int dfm_loss_scale_update(float* amp, int* flag, float growth, float backoff, int interval, dfm_stream_t stream);
 
-/* ---- optimizer options (csrc/optim.hip): gradient accumulation, global-norm clipping, weight EMA.
+/* ---- optimizer options: gradient accumulation, global-norm clipping, weight EMA.
  * What a step decides is read on the device, so one captured graph serves every micro-step:
  *   win[2]  int32 {micro_index, accum_steps}; a kernel taking `win` does nothing unless
  *           micro_index == accum_steps - 1 (NULL: no window, always the last micro-step)
@@ -803,15 +804,17 @@ int dfm_grad_sumsq(long n, const float* g, float* part, int* flag, const int* wi
 int dfm_grad_clip_coef(int npart, const float* part, float grad_scale, const float* amp, float max_norm,
                        float* clip_state, const int* win, dfm_stream_t stream);
 /* dfm_adamw_dev / dfm_adamw_amp (amp and flag both given or both NULL) with the options, each off
- * when its pointer is NULL and then bit-identical to those: the gradient times clip_state[1]
+ * when its pointer is NULL: the gradient times clip_state[1]
  * (clip_grad_norm_'s in-place scaling); no write unless win says last micro-step; ema = ema_decay *
  * ema + (1 - ema_decay) * p_new in the same pass (ema.lerp_(p, 1 - decay) after optimizer.step());
- * clear_g: g is the accumulation buffer and is zeroed once consumed, also by a step that flag skips. */
+ * clear_g: g is the accumulation buffer and is zeroed once consumed, also by a step that flag skips.
+ * With clip_state, win, ema and clear_g all off it launches what dfm_adamw_dev / dfm_adamw_amp
+ * launch: the instantiation that holds no option code and never writes g. */
 int dfm_adamw_opt(long n, float* p, float* g, int clear_g, float* m, float* v, const float* hyper,
                   const float* amp, const int* flag, const float* clip_state, const int* win, float* ema,
                   float ema_decay, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
                   void* copy, int copy_dtype, dfm_stream_t stream);
-/* dfm_loss_scale_update once per accumulation window (GradScaler.update after the window's step). */
+/* dfm_loss_scale_update (win NULL) once per accumulation window (GradScaler.update after the window's step). */
 int dfm_loss_scale_update_win(float* amp, int* flag, float growth, float backoff, int interval, const int* win,
                               dfm_stream_t stream);
 

@@ -161,32 +161,38 @@ def _grads(n, steps=3):
     return [_randn(n, 20 + t, 0.3) for t in range(steps)]
 
 
+def _adamw(K, b, g, gscale, opt, **kw):
+    """K.adamw(hyper=...) on the buffers b, asserting with the launch tracer which instantiation of the
+    one update kernel ran: without this a dispatch slip would compare a kernel with itself."""
+    import kernel_variants as kv
+    with kv.Trace() as tr:
+        K.adamw(b.p, g, b.m, b.v, 0.0, B1, B2, EPS, WD, 1, gscale, b.copy, hyper=b.hyper, **kw)
+    tc = {torch.bfloat16: "unsigned short", torch.float16: "f16_t"}[b.copy.dtype]
+    assert tr.launched == [f"adamw_kernel<{tc}, {'true' if opt else 'false'}>"], tr.launched
+
+
 @pytest.mark.parametrize("n", SIZES)
 def test_update_variant_bit_relations(n):
     from dformer_amd import kernels as K
     gs = _grads(n)
-    ref, opt, one = _Bufs(n), _Bufs(n), _Bufs(n)
+    ref, one = _Bufs(n), _Bufs(n)
     clip1 = torch.tensor([5.0, 1.0], device=_dev())
     for t, g in enumerate(gs):
-        for b in (ref, opt, one):
+        for b in (ref, one):
             b.hyper[1] = float(t + 1)
-        K.adamw(ref.p, g, ref.m, ref.v, 0.0, B1, B2, EPS, WD, 1, 0.5, ref.copy, hyper=ref.hyper)
-        K.adamw_opt(opt.p, g.clone(), opt.m, opt.v, opt.hyper, B1, B2, EPS, WD, 0.5, opt.copy)
-        K.adamw_opt(one.p, g.clone(), one.m, one.v, one.hyper, B1, B2, EPS, WD, 0.5, one.copy, clip_state=clip1)
-        assert ref.same(opt), f"options off differs from dfm_adamw_dev at step {t + 1}"
-        assert ref.same(one), f"coef = 1 differs from no coef at step {t + 1}"
+        _adamw(K, ref, g, 0.5, opt=False)
+        _adamw(K, one, g.clone(), 0.5, opt=True, clip_state=clip1)
+        assert ref.same(one), f"coef = 1 on the option kernel differs from the plain kernel at step {t + 1}"
     # inside a window: nothing is written; on its last micro-step: the update, and acc cleared
     win = torch.tensor([0, 2], device=_dev(), dtype=torch.int32)
     w = _Bufs(n)
     acc = gs[0].clone()
-    K.adamw_opt(w.p, acc, w.m, w.v, w.hyper, B1, B2, EPS, WD, 0.5, w.copy, win=win, ema=w.ema, ema_decay=0.9,
-                clear_g=True)
+    _adamw(K, w, acc, 0.5, opt=True, win=win, ema=w.ema, ema_decay=0.9, clear_g=True)
     fresh = _Bufs(n)
     assert w.same(fresh) and torch.equal(w.ema, fresh.ema) and torch.equal(acc, gs[0])
     win[0] = 1
-    K.adamw_opt(w.p, acc, w.m, w.v, w.hyper, B1, B2, EPS, WD, 0.5, w.copy, win=win, ema=w.ema, ema_decay=0.9,
-                clear_g=True)
-    K.adamw(fresh.p, gs[0], fresh.m, fresh.v, 0.0, B1, B2, EPS, WD, 1, 0.5, fresh.copy, hyper=fresh.hyper)
+    _adamw(K, w, acc, 0.5, opt=True, win=win, ema=w.ema, ema_decay=0.9, clear_g=True)
+    _adamw(K, fresh, gs[0], 0.5, opt=False)
     assert w.same(fresh) and not acc.any()
     assert not torch.equal(w.ema, fresh.ema)  # the average moved with the applied step
 
@@ -198,14 +204,53 @@ def test_update_variant_bit_equal_to_amp(n):
     ref, opt = _Bufs(n, torch.float16), _Bufs(n, torch.float16)
     st = [torch.tensor([1024.0, 0.0, 0.0, 0.0], device=_dev()) for _ in range(2)]
     fl = [torch.zeros(1, device=_dev(), dtype=torch.int32) for _ in range(2)]
+    clip1 = torch.tensor([5.0, 1.0], device=_dev())
+    win1 = torch.tensor([0, 1], device=_dev(), dtype=torch.int32)  # a window of one micro-step: always its last
     for t, g in enumerate(gs):
-        K.adamw(ref.p, g, ref.m, ref.v, 0.0, B1, B2, EPS, WD, 1, 1.0, ref.copy, hyper=ref.hyper, amp=st[0], flag=fl[0])
+        _adamw(K, ref, g, 1.0, opt=False, amp=st[0], flag=fl[0])
         K.loss_scale_update(st[0], fl[0], 2.0, 0.5, 2)
-        K.adamw_opt(opt.p, g.clone(), opt.m, opt.v, opt.hyper, B1, B2, EPS, WD, 1.0, opt.copy, amp=st[1], flag=fl[1])
-        K.loss_scale_update_win(st[1], fl[1], 2.0, 0.5, 2)
+        _adamw(K, opt, g.clone(), 1.0, opt=True, amp=st[1], flag=fl[1], clip_state=clip1)
+        K.loss_scale_update(st[1], fl[1], 2.0, 0.5, 2, win=win1)
         assert ref.same(opt), f"step {t + 1}"
         assert torch.equal(st[0], st[1])
     assert st[0].tolist() == [2048.0, 1.0, 3.0, 0.0]  # grew once (interval 2), three applied steps
+
+
+def _raw_adamw(b, g, amp=None, flag=None, opt=False):
+    """dfm_adamw_dev / dfm_adamw_amp (no wrapper of the package calls them any more; they stay in
+    the ABI) or the dfm_adamw_opt call that stands for them, through the library directly."""
+    from dformer_amd import _lib
+    from dformer_amd._lib import dtype_code, ptr, stream
+    lib, tail = _lib.lib, (B1, B2, EPS, WD, 0.5, ptr(b.copy), dtype_code(b.copy), stream())
+    bufs = (b.p.numel(), ptr(b.p), ptr(g), ptr(b.m), ptr(b.v), ptr(b.hyper))
+    if opt:
+        st = lib.dfm_adamw_opt(*bufs[:3], 0, *bufs[3:], ptr(amp), ptr(flag), None, None, None, 0.0, *tail)
+    elif amp is not None:
+        st = lib.dfm_adamw_amp(*bufs, ptr(amp), ptr(flag), *tail)
+    else:
+        st = lib.dfm_adamw_dev(*bufs, *tail)
+    _lib.check(st, "raw adamw")
+
+
+@pytest.mark.parametrize("copy_dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("n", [257, 70_001])
+def test_abi_entry_points_give_the_wrapper_bits(n, copy_dtype):
+    """dfm_adamw_dev and dfm_adamw_amp against dfm_adamw_opt with the same arguments, 3 steps."""
+    amp = torch.tensor([4.0, 0.0, 0.0, 0.0], device=_dev())
+    flag = torch.zeros(1, device=_dev(), dtype=torch.int32)
+    dev, dev_opt, hal, hal_opt = (_Bufs(n, copy_dtype) for _ in range(4))
+    for t, g in enumerate(_grads(n)):
+        for b in (dev, dev_opt, hal, hal_opt):
+            b.hyper[1] = float(t + 1)
+        amp[2] = float(t)  # applied steps so far: the amp path's step count is amp[2] + 1
+        _raw_adamw(dev, g)
+        _raw_adamw(dev_opt, g, opt=True)
+        _raw_adamw(hal, g * 4.0, amp, flag)
+        _raw_adamw(hal_opt, g * 4.0, amp, flag, opt=True)
+        assert dev.same(dev_opt), f"dfm_adamw_dev, step {t + 1}"
+        assert hal.same(hal_opt), f"dfm_adamw_amp, step {t + 1}"
+    assert not dev.same(_Bufs(n, copy_dtype)) and not hal.same(_Bufs(n, copy_dtype))  # the updates were applied
+    assert torch.equal(dev.p, hal.p)  # g * 4 unscaled by amp[0] = 4 is g, exactly
 
 
 def _err(x, x64):
@@ -215,8 +260,8 @@ def _err(x, x64):
 @pytest.mark.parametrize("n", [257, 70_001])
 def test_update_variant_against_fp64_torch(n):
     """clip_grad_norm_ + torch.optim.AdamW in fp64 on the same gradients for 3 steps, plus the
-    ema.lerp_ recursion. The existing dfm_adamw_dev (fed the fp64-clipped gradients rounded to fp32)
-    is measured against the same trajectory; the new kernel, which clips by itself, stays within 2 x
+    ema.lerp_ recursion. The plain kernel (fed the fp64-clipped gradients rounded to fp32) is
+    measured against the same trajectory; the option kernel, which clips by itself, stays within 2 x
     its error: the arithmetic is identical up to one extra multiply."""
     from dformer_amd import kernels as K
     gs = _grads(n)
@@ -233,15 +278,14 @@ def test_update_variant_against_fp64_torch(n):
         ema64.lerp_(p64.detach(), 1 - d)
         for b in (old, new):
             b.hyper[1] = float(t + 1)
-        K.adamw(old.p, p64.grad.float(), old.m, old.v, 0.0, B1, B2, EPS, WD, 1, 1.0, old.copy, hyper=old.hyper)
+        _adamw(K, old, p64.grad.float(), 1.0, opt=False)
         clip, _ = _norm(K, [g], max_norm=max_norm)
-        K.adamw_opt(new.p, g.clone(), new.m, new.v, new.hyper, B1, B2, EPS, WD, 1.0, new.copy, clip_state=clip,
-                    ema=new.ema, ema_decay=d)
+        _adamw(K, new, g.clone(), 1.0, opt=True, clip_state=clip, ema=new.ema, ema_decay=d)
     st = topt.state[p64]
     for name, xo, xn, x64 in (("p", old.p, new.p, p64.detach()), ("m", old.m, new.m, st["exp_avg"]),
                               ("v", old.v, new.v, st["exp_avg_sq"])):
         eo, en = _err(xo, x64), _err(xn, x64)
-        print(f"update n={n} {name}: dfm_adamw_dev {eo:.3e}, dfm_adamw_opt {en:.3e}")
+        print(f"update n={n} {name}: plain {eo:.3e}, with options {en:.3e}")
         assert en <= 2 * eo, (name, en, eo)
     # the average: a convex combination of the p trajectory (error <= p's) plus, per step, the
     # roundings of d, 1 - d, the product and the fused add
@@ -259,9 +303,9 @@ def _window(K, bufs, acc, grads, win, st, fl, clip, poison=None):
         if poison == ("flag", i):
             fl.fill_(1)
         _norm(K, [acc], gscale=1.0 / len(grads), max_norm=1.0, amp=st, flag=fl, win=win, clip=clip)
-        K.adamw_opt(bufs.p, acc, bufs.m, bufs.v, bufs.hyper, B1, B2, EPS, WD, 1.0 / len(grads), bufs.copy, amp=st,
-                    flag=fl, clip_state=clip, win=win, ema=bufs.ema, ema_decay=0.9, clear_g=True)
-        K.loss_scale_update_win(st, fl, 2.0, 0.5, 2000, win)
+        _adamw(K, bufs, acc, 1.0 / len(grads), opt=True, amp=st, flag=fl, clip_state=clip, win=win, ema=bufs.ema,
+               ema_decay=0.9, clear_g=True)
+        K.loss_scale_update(st, fl, 2.0, 0.5, 2000, win)
 
 
 @pytest.mark.parametrize("how", ["inf_grad", "flag"])

@@ -6,11 +6,11 @@ Two flat groups of --params elements in all (DFormer-Base: 29.8 M, nearly all in
 shadow on the decay group as in the bf16 step. The pieces are timed with HIP events around --inner
 back-to-back launches, alternated in one process, median of --reps regions:
 
-  adamw_dev        the tail with the options off (one launch per group, every call)
+  adamw_plain      the tail with the options off (one launch per group, every call)
   accumulate       acc += g (every call with accum_steps > 1)
   norm             sum of squares, both stages (the window's last call)
-  adamw_opt        the update with clip coefficient, EMA and the accumulator's clear (the window's last call)
-  skipped          norm + adamw_opt launched inside a window: they return at once (every other call)
+  adamw_options    the update with clip coefficient, EMA and the accumulator's clear (the window's last call)
+  skipped          norm + adamw_options launched inside a window: they return at once (every other call)
 
 Each piece's algorithmic bytes (what kernels.py accounts) over its time is the achieved bytes/s; the
 share of HBM rate is against the 6.3 TB/s a float4 copy reaches on the MI355X (8.0 TB/s on paper).
@@ -61,7 +61,7 @@ def main():
     inside = torch.tensor([0, a.accum], device=DEV, dtype=torch.int32)
     gscale = 1.0 / a.accum
 
-    def adamw_dev():
+    def adamw_plain():
         for g in groups:
             K.adamw(g.p, g.g, g.m, g.v, 0.0, B1, B2, EPS, WD, 1, 1.0, g.copy, hyper=hyper)
 
@@ -74,18 +74,18 @@ def main():
             K.grad_sumsq(g.acc, part[j * nb:(j + 1) * nb], win=win)
         K.grad_clip_coef(part, gscale, 1.0, clip, win=win)
 
-    def adamw_opt(win=last):
+    def adamw_options(win=last):
         for g in groups:
-            K.adamw_opt(g.p, g.acc, g.m, g.v, hyper, B1, B2, EPS, WD, gscale, g.copy, clip_state=clip, win=win,
-                        ema=g.ema, ema_decay=0.999, clear_g=True)
+            K.adamw(g.p, g.acc, g.m, g.v, 0.0, B1, B2, EPS, WD, 1, gscale, g.copy, hyper=hyper, clip_state=clip,
+                    win=win, ema=g.ema, ema_decay=0.999, clear_g=True)
 
     def skipped():
         norm(inside)
-        adamw_opt(inside)
+        adamw_options(inside)
 
     shadow = 2 * groups[0].p.numel()
-    pieces = {"adamw_dev": (adamw_dev, 28 * n + shadow), "accumulate": (accumulate, 12 * n), "norm": (norm, 4 * n),
-              "adamw_opt": (adamw_opt, 40 * n + shadow), "skipped": (skipped, 0)}
+    pieces = {"adamw_plain": (adamw_plain, 28 * n + shadow), "accumulate": (accumulate, 12 * n), "norm": (norm, 4 * n),
+              "adamw_options": (adamw_options, 40 * n + shadow), "skipped": (skipped, 0)}
     times = {k: [] for k in pieces}
     for it in range(a.reps + 3):
         for name, (fn, _) in pieces.items():  # alternated: every piece sees the same neighbours and clocks
@@ -109,8 +109,8 @@ def main():
             row["share_of_hbm_copy_rate"] = round(nbytes / med[name] / 1e9 / HBM_COPY_TBPS, 3)
         res["pieces"][name] = row
     k = a.accum
-    off = k * med["adamw_dev"]
-    on = k * med["accumulate"] + (k - 1) * med["skipped"] + med["norm"] + med["adamw_opt"]
+    off = k * med["adamw_plain"]
+    on = k * med["accumulate"] + (k - 1) * med["skipped"] + med["norm"] + med["adamw_options"]
     res["window_tail_ms"] = {"options_off": round(off, 4), "all_on": round(on, 4), "extra": round(on - off, 4)}
     text = json.dumps(res, indent=1)
     print(text)
