@@ -816,6 +816,8 @@ extern "C" int dfm_bn_apply(int dtype, long rows, int C, const void* x, long ldx
 
 extern "C" int dfm_bn_bwd_stats(int dtype, long rows, int C, const void* x, long ldx, const void* dy, long lddy,
                                 const float* mean, const float* rstd, float* stats2, void* ws, dfm_stream_t stream) {
+  DFM_CHECK_DTYPE(dtype);
+  DFM_CHECK_ARG(x && dy && mean && rstd && stats2 && ws, "dfm_bn_bwd_stats: null argument");
   hipStream_t s = (hipStream_t)stream;
   DFM_DTYPE_SWITCH(dtype, T, return colred<T, 2>(rows, C, x, ldx, dy, lddy, mean, rstd, 1, stats2, 0, ws, s));
 }

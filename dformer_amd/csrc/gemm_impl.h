@@ -1402,8 +1402,6 @@ int gemm_group_typed(int n, const DfmGemmDesc* d, const void* const* A, const vo
   }
   // (weight gradients on the ring kernel in 128 x 128 tiles measured 472.3 / 472.5 vs 472.8 / 473.0
   // images/s: the register-staged kernel stays)
-  if (ak && bk) return group_launch<T, true, true>(n, d, A, B, C, (char*)ws, s);
-  if (ak) return group_launch<T, true, false>(n, d, A, B, C, (char*)ws, s);
   if (bk) return group_launch<T, false, true>(n, d, A, B, C, (char*)ws, s);
   return group_launch<T, false, false>(n, d, A, B, C, (char*)ws, s);
 }

@@ -763,12 +763,14 @@ def _check(cid, chk):
     # only, and a correct kernel reaches twice that just above a power of two (measured: 1.4 to 1.96 times
     # the bound without this term on every bf16 GEMM, fp32 at 0.008, fp16 within 1). The term adds what
     # u_out |r| leaves out of the half ulp (nothing for fp16 and fp32 above their subnormal range); the
-    # binade is that of |r| plus the accumulation bound, the largest value that can have been rounded.
+    # binade is that of |r| plus the accumulation bound (and the check's extra term, which moves the value
+    # before it is rounded as well), the largest value that can have been rounded.
+    if chk.extra is not None:
+        acc = acc + chk.extra.to(got.device)
+        bound = bound + chk.extra.to(got.device)
     p, emin = ROUNDING[chk.u]
     e = torch.floor(torch.log2((ref.abs() + acc).clamp_min(2.0 ** emin)))
     bound = bound + (torch.exp2(e - p) - chk.u * ref.abs()).clamp_min(0.0)
-    if chk.extra is not None:
-        bound = bound + chk.extra.to(got.device)
     exact = bound == 0
     if (err[exact] != 0).any():
         return math.inf
