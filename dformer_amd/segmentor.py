@@ -8,7 +8,8 @@ materialised when `return_logits` is True (the loss itself is fused and never ne
 With `decoder == "ham"` and a non-zero `cfg.aux_rate` an auxiliary FCNHead reads the stage-2 map and the
 training loss is CE(main) + aux_rate * CE(aux) (builder.py:138-143, 204-207, 231-232); no eval path runs it.
 `criterion` is the reference's plain CrossEntropyLoss or a losses.FusedSegLoss (class weights, label
-smoothing, hard example mining; applied to the main and the aux loss, all on the fused kernels).
+smoothing, hard example mining, focal and Tversky / Dice terms; applied to the main and the aux loss, all on
+the fused kernels).
 `decoder == "UPernet"` builds UPerHead on all four maps (logits at 1/4 resolution) and always the aux head
 with aux_rate 0.4 (builder.py:145-152).
 """
@@ -167,13 +168,27 @@ class EncoderDecoder(nn.Module):
         # a FusedSegLoss criterion's options apply to both heads (builder.py:230-232 calls the one criterion
         # on each); the aux head is mined on its own probabilities
         opts = self.criterion.kernel_options(rows.device) if isinstance(self.criterion, FusedSegLoss) else ()
-        loss = SegLossFn.apply(rows.contiguous(), B, h, w, label.long(), self.ignore_index, *opts)
+        if opts and self.criterion.has_terms():
+            head_loss = self._terms_loss  # a focal or region term: dformer_amd.criterion, loaded on first use
+        else:
+            def head_loss(r, B, h, w, label, opts):
+                return SegLossFn.apply(r, B, h, w, label, self.ignore_index, *opts)
+        loss = head_loss(rows.contiguous(), B, h, w, label.long(), opts)
         if aux is not None:  # builder.py:231-232: + aux_rate * CE(up(aux)) over the same valid pixels
             arows, (B, ah, aw) = _nhwc_rows(aux)
-            loss = loss + self.aux_rate * SegLossFn.apply(arows.contiguous(), B, ah, aw, label.long(),
-                                                          self.ignore_index, *opts)
+            loss = loss + self.aux_rate * head_loss(arows.contiguous(), B, ah, aw, label.long(), opts)
         out = self._upsample(low.detach(), rgb.shape[-2:]) if self.return_logits else low
         return loss, out
+
+    def _terms_loss(self, rows, B, h, w, label, opts):
+        """One head's loss under a FusedSegLoss with a focal or region term. focal_gamma > 0: the new function
+        alone computes the pixel and the region term in one pass; region only: SegLossFn as always (weights,
+        smoothing, mining) plus the region term on the original labels."""
+        crit = self.criterion
+        terms = crit.fused_terms(rows, B, h, w, label, opts[0])
+        if crit.focal_gamma > 0.0:
+            return terms
+        return SegLossFn.apply(rows, B, h, w, label, self.ignore_index, *opts) + terms
 
     # ------------------------------------------------------------------ few-shot episodes (builder.py:210-320)
     def encode(self, rgb, modal_x):
@@ -223,6 +238,10 @@ class EncoderDecoder(nn.Module):
         One encoder pass over the B*S + B images; the prototype pooling, the cosine branch and the loss run on
         stage-3 sized tensors; nothing is read back to the host."""
         alpha, temperature = self._fss_config()
+        if isinstance(self.criterion, FusedSegLoss) and self.criterion.has_terms():
+            raise NotImplementedError("meta_forward: the episode loss has its own kernels and takes no focal or "
+                                      "region term; they would be silently dropped (use a FusedSegLoss without "
+                                      "focal_gamma / region)")
         if s_rgb.dim() != 5 or s_mask.dim() != 4 or tuple(s_mask.shape[:2]) != tuple(s_rgb.shape[:2]):
             raise ValueError(f"meta_forward: s_rgb {tuple(s_rgb.shape)} / s_mask {tuple(s_mask.shape)} are not "
                              "[B, S, 3, H, W] / [B, S, H, W]")
